@@ -2,6 +2,7 @@
 """Headline benchmark: training clips/sec of the RGB+Depth token-fusion step (BASELINE.json).
 
     python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (also writes the last timed step's outputs)
 
 A step = one full training step of r3d_amd's FUTR on one batch of synthetic clips: forward + 3 losses + backward +
 AdamW (+ gradient all-reduce over RCCL when N>1), dropout active (the reference's first-epoch state), inputs already
@@ -162,6 +163,42 @@ def erank_field(eng):
                 us=sorted(ts)[2], matrix=[N, H], kernel=kernel, in_step=False,
                 note="measured after the timed region on the last step's fused tokens; the headline step runs with "
                      "erank_weight = 0 (the reference's loss, SURVEY.md F1)")
+
+
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: everything written, .npy headers included
+
+
+def dump_outputs(eng, out_dir, skip=()):
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name>.npy in float32 / float64: the four
+    losses and the counters (train_step's return), the forward outputs seg / action / duration, and every parameter the
+    step updated (param.<name>).  An array larger than its share of DUMP_BYTES is written as a fixed sample of its
+    flattened elements: one per equal stratum, at an offset drawn from a generator seeded with 0 -- the same elements on
+    every run of the same configuration.  Returns (arrays, bytes) written."""
+    import numpy as np
+    w, a, K, Q = eng.last["w"], eng.arena, eng.K, eng.Q
+    arrays = dict(losses=w.loss, counts=w.counts, seg=w.seg.view(w.B, w.S, K),
+                  action=w.actdur[:, :K].reshape(w.B, Q, K), duration=w.actdur[:, K].reshape(w.B, Q))
+    arrays.update({f"param.{n}": a.p(n) for n in a.live_names if n not in skip})
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].numel(), k))
+    left, wrote = DUMP_BYTES, 0
+    for i, name in enumerate(names):
+        t = arrays[name].detach()
+        t = t.float() if t.dtype == torch.float32 else t.double()
+        share = left // (len(names) - i) - 256                     # 256: room for the .npy header
+        n, item = t.numel(), t.element_size()
+        if n * item > share:
+            k = max(1, share // item)
+            lo = np.arange(k, dtype=np.int64) * n // k
+            hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+            idx = lo + (np.random.default_rng(0).random(k) * (hi - lo)).astype(np.int64)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        path = os.path.join(out_dir, f"{name}.npy")
+        np.save(path, t.cpu().numpy())
+        size = os.path.getsize(path)
+        left -= size
+        wrote += size
+    return len(names), wrote
 
 
 PMC_TABLE = os.path.join("profiles", "r03_pmc_hbm.json")
@@ -355,6 +392,10 @@ def main():
                          "reference's loss")
     ap.add_argument("--erank-warm", action="store_true",
                     help="with --erank-weight: warm-start the Jacobi sweep from the previous step's singular basis")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (losses, counters, forward outputs, "
+                         "updated parameters) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; the inputs are "
+                         "seeded, so two builds run with the same arguments can be compared output for output")
     ap.add_argument("--probe-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-probe", action="store_true",
                     help="multi-GPU: skip the child-process rehearsal of the RCCL step (needed under a profiler)")
@@ -362,6 +403,8 @@ def main():
                     help="rehearsal: run the multi-rank flow (process group, exchanges, graphs around them) with however "
                          "many ranks there are, even one")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.probe_child and os.environ.get("R3D_PROBE_FAIL") == "1":      # (test hook: a failing rehearsal)
         sys.exit(3)
     # libraries write to fd 1 (RCCL prints a version banner there): stdout is kept for the one JSON line
@@ -690,6 +733,12 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if a.dump_outputs and rank == 0 and not a.probe_child:
+        # before anything below runs more steps (the one-step-per-graph A/B) or writes into the step's buffers (the
+        # kernel timings); a pixel-sharded rank holds only its columns of depth_projection.weight
+        n_arr, n_bytes = dump_outputs(eng, a.dump_outputs, skip=("depth_projection.weight",) if tp is not None else ())
+        print(f"[bench] last timed step: {n_arr} arrays, {n_bytes / 1e6:.1f} MB -> {a.dump_outputs}", file=sys.stderr,
+              flush=True)
     single = None
     if run_many and not dist_on and not a.probe_child:
         # A/B beside the headline: the same K steps replayed as ONE step per hipGraph launch -- what train()'s _GraphedSteps

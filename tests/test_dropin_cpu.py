@@ -33,9 +33,9 @@ print(json.dumps(out))
 '''
 
 
-def test_reference_import_lines_resolve_through_dropin():
+def test_reference_import_lines_resolve_through_dropin(tmp_path):
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "dropin"), ROOT]))
-    r = subprocess.run([sys.executable, "-c", SCRIPT], env=env, capture_output=True, text=True, cwd="/tmp", timeout=300)
+    r = subprocess.run([sys.executable, "-c", SCRIPT], env=env, capture_output=True, text=True, cwd=str(tmp_path), timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     got = json.loads(r.stdout.strip().split("\n")[-1])
     import numpy as np
