@@ -637,6 +637,33 @@ int r3d_embed_gather_fwd(const float* weight, int n_embed, const int64_t* idx, c
 int r3d_embed_gather_bwd(const float* d_out, int ldd, const int64_t* idx, float* d_weight, int n_embed, int rows, int H,
                          void* stream);
 
+/* ---- device-resident clip store (r3d_amd/clipcache.py; clipcache.hip) ------------------------------------------------
+ * The padded batch of the reference's dataset + my_collate (data/basedataset_darai_depth.py:110-130,174-206) gathered from
+ * frame pools in device memory, all five tensors in ONE launch:
+ *   features            [B, S_f, D]  row (b, s) = rgb_pool[ids_f[off_f[items[b]] + s]]     or zeros past the item's length
+ *   depth               [B, S_d, P]  row (b, s) = depth_pool[ids_d[off_d[items[b]] + s]]   or zeros
+ *   past_label          [B, S_l]     lab[off_l[items[b]] + s]                              or pad_idx
+ *   trans_future_dur    [B, S_q]     q_dur[off_q[items[b]] + s]                            or (float)pad_idx
+ *   trans_future_target [B, S_q]     q_tgt[off_q[items[b]] + s]                            or pad_idx
+ * off_* are CSR offsets of n_items + 1 entries (off[0] = 0, off[n_items] = the table's length); items may repeat.  An item id
+ * outside [0, n_items) or a pool id outside [0, F) reads nothing and yields padding.  Pools and outputs are dense fp32 rows;
+ * any row length collates (16-byte loads when D / P % 4 == 0 and the bases are 16-byte aligned, dword loads otherwise).
+ * Extents of 0 (B, S_*, D, P, F) are legal and enqueue nothing for that part.  R3D_EINVAL: a negative extent, a NULL pool
+ * with F > 0 rows, or a NULL table / output that a non-empty part would touch. */
+typedef struct r3d_clip_collate_job {
+    const float* rgb_pool; int64_t F_rgb, D;
+    const float* depth_pool; int64_t F_dep, P;
+    int64_t n_items;
+    const int64_t* off_f; const int64_t* ids_f;
+    const int64_t* off_d; const int64_t* ids_d;
+    const int64_t* off_l; const int64_t* lab;
+    const int64_t* off_q; const float* q_dur; const int64_t* q_tgt;
+    const int64_t* items; int64_t B;
+    int64_t S_f, S_d, S_l, S_q, pad_idx;
+    float* features; float* depth; int64_t* past_label; float* trans_future_dur; int64_t* trans_future_target;
+} r3d_clip_collate_job;
+int r3d_clip_collate(const r3d_clip_collate_job* job, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

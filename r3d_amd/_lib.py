@@ -153,6 +153,15 @@ class LnFinalizeJob(C.Structure):
     _fields_ = [("ws", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("rows", C.c_int32), ("H", C.c_int32)]
 
 
+class ClipCollateJob(C.Structure):
+    """struct r3d_clip_collate_job"""
+    _fields_ = ([("rgb_pool", C.c_void_p), ("F_rgb", C.c_int64), ("D", C.c_int64),
+                 ("depth_pool", C.c_void_p), ("F_dep", C.c_int64), ("P", C.c_int64), ("n_items", C.c_int64)] +
+                [(n, C.c_void_p) for n in "off_f ids_f off_d ids_d off_l lab off_q q_dur q_tgt items".split()] +
+                [(n, C.c_int64) for n in "B S_f S_d S_l S_q pad_idx".split()] +
+                [(n, C.c_void_p) for n in "features depth past_label trans_future_dur trans_future_target".split()])
+
+
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 
 _I, _L, _F, _P, _D = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_double
@@ -254,6 +263,7 @@ _SIGNATURES = {
     "r3d_erank_lds_bytes_v": ([_I, _I], C.c_int64),
     "r3d_erank_jacobi_warm": ([_P, _I, _L, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P], C.c_int),
     "r3d_erank_vt_polish": ([_P, _P, _P, _L, _P], C.c_int),
+    "r3d_clip_collate": ([C.POINTER(ClipCollateJob), _P], C.c_int),
 }
 
 EXPORTS = tuple(_SIGNATURES)
