@@ -35,6 +35,29 @@ def is_live(name):
     return name.startswith(LIVE_PREFIXES)
 
 
+# Shape admission of the hidden-128 chain launches (csrc/fuser_chain.hip, csrc/decoder_chain.hip), host-only so that the
+# routing of every batch shape can be checked without a GPU (tests/test_chain_admission_cpu.py).
+BWD_BF3_MAX_K = 32              # the bf16x3 backward chain holds (Wseg)^T as ONE 32-wide plane tile (fuser_chain.hip:1039)
+
+
+def fuser_chain_shape_ok(B, S, H, K, Q, heads, bn=False):
+    return bool(not bn and H // heads == 16 and ops.fuser_chain_supported(B * S, H, K, B, Q, heads))
+
+
+def decoder_chain_shape_ok(B, S, H, Q, heads, L):
+    return bool(L == 1 and H // heads == 16 and B * Q <= 1024 and ops.decoder_chain_supported(H, Q, heads, S))
+
+
+def bwd_chain_bf3(chain_bf3, K):
+    """Backward fuser chain on the bf16 matrix cores (True) or in exact fp32 (False); the forward is not limited by K."""
+    return bool(chain_bf3 and K <= BWD_BF3_MAX_K)
+
+
+def tail_in_decoder_chain(B, H, K, Q):
+    """A training step's tail forward, losses and tail backward fit ONE launch (and with the decoder chain, its launch)."""
+    return ops.tail_losses_supported(H, K + 1, Q, B * Q)
+
+
 class ParamArena:
     """Flat arenas; live parameters first (AdamW touches only that prefix), depth_projection.weight last among them
     so that everything else forms one contiguous all-reduce bucket that is ready before the big weight gradient."""
@@ -312,6 +335,11 @@ class FusionEngine:
         self.last = None
         self._adam = None
         self._drop_ready = None           # workspace whose dropout pool already holds the masks of the next forward
+        # high-water mark of the pos_embedding gradient rows a backward has written: a step only writes its first S rows
+        # (:190), so every backward clears rows [S, pos_grad_rows) left by a longer earlier batch (monotone, so a step
+        # captured in a hipGraph clears what any step before its capture could have written; train() re-captures when it
+        # grows)
+        self.pos_grad_rows = 0
         a = self.arena
         K, H = self.K, self.H
         o_w = a.offsets["fc.weight"][0]
@@ -706,14 +734,13 @@ class FusionEngine:
             self._tail_pending = False
 
     def _chain_shape_ok(self, w):
-        return bool(not self.bn and self.dh == 16 and ops.fuser_chain_supported(w.N, self.H, self.K, w.B, self.Q, self.heads))
+        return fuser_chain_shape_ok(w.B, w.S, self.H, self.K, self.Q, self.heads, self.bn)
 
     def _chain_ok(self, w):
         return bool(self.use_fuser_chain and self._chain_shape_ok(w))
 
     def _dec_chain_ok(self, w):
-        return bool(self.use_decoder_chain and self.L == 1 and self.dh == 16 and w.BQ <= 1024 and
-                    ops.decoder_chain_supported(self.H, self.Q, self.heads, w.S))
+        return bool(self.use_decoder_chain and decoder_chain_shape_ok(w.B, w.S, self.H, self.Q, self.heads, self.L))
 
     def _dec_chain(self, w, drop):
         """The argument block of the decoder chain kernel for this workspace (one per dropout state)."""
@@ -858,7 +885,7 @@ class FusionEngine:
                 drop_now = self.last_drop_flag
                 w._tail_done = False
                 w._tail_deferred = bool(self.use_fused_tail and self.defer_tail and self._fw["mode"] == "train" and
-                                        hasattr(w, "glayers") and ops.tail_losses_supported(H, self.K + 1, Q, BQ))
+                                        hasattr(w, "glayers") and tail_in_decoder_chain(B, H, self.K, Q))
                 w._dec_key_labels = key_labels
                 if w._tail_deferred:
                     w._dec_deferred = True
@@ -893,7 +920,7 @@ class FusionEngine:
                 # last norm3 + decoder.norm (:182-183) + anticipation heads (:219-226, fc | fc_len = one [K+1, H] product)
                 w._tail_done = False
                 w._tail_deferred = bool(self.defer_tail and self._fw["mode"] == "train" and hasattr(w, "glayers")
-                                        and ops.tail_losses_supported(H, self.K + 1, Q, BQ))
+                                        and tail_in_decoder_chain(B, H, self.K, Q))
                 if w._tail_deferred:
                     return                          # runs inside losses()
                 ops.decoder_tail_fwd(c["t3_pre"], a.p(pl + "norm3.weight"), a.p(pl + "norm3.bias"),
@@ -1206,6 +1233,9 @@ class FusionEngine:
         st = self.last
         w, a, H, Q, K, heads, dh, ws = st["w"], self.arena, self.H, self.Q, self.K, self.heads, self.dh, self.ws
         B, S, N, BQ = w.B, w.S, w.N, w.BQ
+        if S < self.pos_grad_rows:                # (the reference: zero_grad(), and its [:, :S] slice leaves them 0)
+            a.g("pos_embedding")[0, S:self.pos_grad_rows].zero_()
+        self.pos_grad_rows = max(self.pos_grad_rows, S)
         ext_grads = d_seg is not None or d_actdur is not None       # (autograd path: gradients handed in by the caller)
         if d_seg is not None and d_seg.data_ptr() != w.d_seg.data_ptr():
             w.d_seg.copy_(d_seg)
@@ -1325,7 +1355,7 @@ class FusionEngine:
             # and the query-side branch, in ONE launch (csrc/fuser_chain.hip)
             c, gl, pl = w.layers[0], w.glayers[0], "transformer.decoder.layers.0."
             er = bool(st.get("erank"))
-            bf3 = bool(self.chain_bf3 and K <= 32)
+            bf3 = bwd_chain_bf3(self.chain_bf3, K)
             key = ("bwd_chain", bool(drop), er, bf3)
             if key not in w.tables:
                 pls = self.chain_planes() if bf3 else None

@@ -107,6 +107,7 @@ class UnsupDepthEngine:
         self.grad_hook = None
         self.tp = None
         self._drop_ready = None
+        self.pos_grad_rows = 0            # high-water mark of the pos_embedding gradient rows written (see engine.py)
         self.last = None
         a, K, H = self.arena, self.K, self.H
         o_w = a.offsets["fc.weight"][0]
@@ -302,6 +303,9 @@ class UnsupDepthEngine:
             dy, dy2 = gl["sain"], gl["t1pre"]           # d t3 of layer l-1 = through the queries + the residual
         # ---- learned positional embedding (:104): column sums over the clips of d (memory + pos)
         ops.rowmod_sum(w.d_mp, S, a.g("pos_embedding")[0, :S])
+        if S < self.pos_grad_rows:                 # rows a longer earlier batch wrote (the reference's zero_grad() zeroes them)
+            a.g("pos_embedding")[0, S:self.pos_grad_rows].zero_()
+        self.pos_grad_rows = max(self.pos_grad_rows, S)
         # ---- memory: decoder part + segmentation head part; through the encoding's dropout and the ReLU (:97-99)
         wgrad(w.d_seg, w.mem, a.g("fc_seg.weight"), a.g("fc_seg.bias"))
         ops.gemm(GEMM_NN, w.d_seg, a.p("fc_seg.weight"), w.d_mem, res1=w.d_mp, ws=ws)

@@ -55,6 +55,13 @@ def _to_dev(data, device):
             trans_future_target.to(device).long().contiguous())
 
 
+def _graph_key(eng, hyper):
+    """What a captured step depends on besides its batch shape: the AdamW hyper-parameters and the engine's high-water
+    mark of pos_embedding gradient rows (a step clears rows [S, mark) as the mark stood AT CAPTURE, so a longer batch seen
+    since then forces a re-capture)."""
+    return (hyper, getattr(eng, "pos_grad_rows", 0))
+
+
 class _GraphedSteps:
     """Replays the fused training step (forward + losses + backward + AdamW + epoch accumulators) as ONE hipGraph per
     batch shape.  Enqueued launch by launch from Python the 36-launch step is bound by the host (measured 1.68 ms/step
@@ -84,7 +91,8 @@ class _GraphedSteps:
         eng.set_lr(lr)
         if self.dp is not None and self.rs is None:
             return self._step_dp(st, lr, hyper, training)
-        if st["graph"] is not None and st["hyper"] == hyper:
+        gkey = _graph_key(eng, hyper)
+        if st["graph"] is not None and st["hyper"] == gkey:
             st["graph"].replay()
             return
         eng._drop_ready = None
@@ -93,15 +101,15 @@ class _GraphedSteps:
                                       after_losses=self._accumulate, stage_den=True, prefill_dropout=False)
         else:
             run = lambda: self._enqueue(st["buf"], lr, hyper, training)     # noqa: E731
-        if st["seen"] == 0 or st["hyper"] not in (None, hyper):
+        if st["seen"] == 0 or st["hyper"] not in (None, gkey):
             run()                                                           # eager: sizes every workspace
-            st["seen"], st["hyper"], st["graph"] = 1, hyper, None
+            st["seen"], st["hyper"], st["graph"] = 1, gkey, None
             return
         g = torch.cuda.CUDAGraph()
         torch.cuda.synchronize()
         with torch.cuda.graph(g):
             run()
-        st["graph"], st["hyper"] = g, hyper
+        st["graph"], st["hyper"] = g, gkey
         g.replay()
 
     def _accumulate(self, loss, counts):
@@ -124,12 +132,13 @@ class _GraphedSteps:
         def part3():
             eng.adamw(lr, wd, betas=betas, eps=eps, grad_scale=dp.grad_scale, ticked=True)
         eng._drop_ready = None
+        gkey = _graph_key(eng, hyper)
         hook, eng.grad_hook = eng.grad_hook, None            # the exchanges are issued here, between the graphs
         try:
-            if st["graph"] is None or st["hyper"] != hyper:
-                if st["seen"] == 0 or st["hyper"] not in (None, hyper):
+            if st["graph"] is None or st["hyper"] != gkey:
+                if st["seen"] == 0 or st["hyper"] not in (None, gkey):
                     g1 = g2 = g3 = None                          # first step of this shape: eager
-                    st["seen"], st["hyper"], st["graph"] = 1, hyper, None
+                    st["seen"], st["hyper"], st["graph"] = 1, gkey, None
                 else:
                     torch.cuda.synchronize()
                     g1, g2, g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -139,7 +148,7 @@ class _GraphedSteps:
                         eng.backward_depth_wgrad()
                     with torch.cuda.graph(g3):
                         part3()
-                    st["graph"], st["hyper"] = (g1, g2, g3), hyper
+                    st["graph"], st["hyper"] = (g1, g2, g3), gkey
             else:
                 g1, g2, g3 = st["graph"]
             (g1.replay if g1 is not None else part1)()
@@ -272,14 +281,15 @@ class _ShardedSteps:
             rs.run(st["feats"], *buf[1:], self.pad_idx, training, slot=s, lr=lr, hyper=hyper, after_losses=self._accumulate,
                    stage_den=False, prefill_dropout=False)
         eng._drop_ready = None
+        gkey = _graph_key(eng, hyper)
         if not self.use_graphs:
             run()
-        elif st["G"][s] is not None and st["hyper"] == hyper:
+        elif st["G"][s] is not None and st["hyper"] == gkey:
             st["G"][s].replay()
-        elif st["runs"][s] == 0 or st["hyper"] not in (None, hyper):
+        elif st["runs"][s] == 0 or st["hyper"] not in (None, gkey):
             run()                                           # eager: sizes every workspace of this slot
             st["G"] = [None, None]
-            st["hyper"] = hyper
+            st["hyper"] = gkey
         else:
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()

@@ -53,3 +53,31 @@ def assert_close(a, b, rtol=1e-3, atol=1e-5, what=""):
     bad = err > lim
     assert not bool(bad.any()), (f"{what}: {int(bad.sum())}/{a.numel()} outside tol; max abs err "
                                  f"{float(err.max()):.3e}, ref scale {float(b.abs().max()):.3e}")
+
+
+def ffn_kink_units(ffn_pre):
+    """ReLU units of the decoder FFN whose pre-activation is within rounding of zero in the oracle (ffn_pre: the oracle's
+    per-layer pre-activations, aux["ffn_pre"]): the fp32 product may land on the other side of the kink, which flips that
+    unit's contribution (its row of linear1's gradient entirely, everything upstream by the unit's share).  Identified BY
+    CONSTRUCTION from the oracle: |u| <= 2e-6 max|u|, the size of the fp32 accumulation error of a K = H dot product.
+    Returns {(layer, unit)}."""
+    units = set()
+    for l, u in enumerate(ffn_pre):
+        near = (u.abs() <= 2e-6 * float(u.abs().max())).reshape(-1, u.shape[-1])
+        units |= {(l, int(j)) for j in near.any(dim=0).nonzero().flatten()}
+    return units
+
+
+def without_kink_units(n, g, r, units):
+    """(g, r) -- the kernel's and the oracle's gradient of parameter n -- with the rows of linear1 (weight and bias) and the
+    columns of linear2.weight of the kink units removed; other parameters pass through unchanged."""
+    for (l, j) in units:
+        if n in (f"transformer.decoder.layers.{l}.linear1.weight", f"transformer.decoder.layers.{l}.linear1.bias"):
+            keep = torch.ones(r.shape[0], dtype=torch.bool)
+            keep[j] = False
+            g, r = g[keep], r[keep]
+        elif n == f"transformer.decoder.layers.{l}.linear2.weight":
+            keep = torch.ones(r.shape[1], dtype=torch.bool)
+            keep[j] = False
+            g, r = g[:, keep], r[:, keep]
+    return g, r

@@ -10,7 +10,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import futr_oracle as O  # noqa: E402
-from tests.helpers import load_fixture, fixture_params, fixture_batch, stats, assert_close  # noqa: E402
+from tests.helpers import (load_fixture, fixture_params, fixture_batch, stats, assert_close, ffn_kink_units,  # noqa: E402
+                           without_kink_units)
 
 RTOL = 1e-3
 
@@ -225,31 +226,16 @@ def test_step_parity_baseline_sizes(B, S, H, K, n_dec, oracle_lib):
     close_rel(eng.last["w"].fused.view(B, S, H), oaux["fused"].detach(), f"H{H}/fused")
     assert_close(loss[3].cpu(), float(ores["loss"]), 1e-3, 1e-6, "total loss")
     assert torch.equal(eng.last["idx"][0].cpu(), oaux["idx_rgb"]) and torch.equal(eng.last["idx"][1].cpu(), oaux["idx_dep"])
-    # ReLU units of the decoder FFN whose pre-activation is within rounding of zero in the oracle: the fp32 product here may
-    # land on the other side of the kink, which flips that unit's contribution (its row of linear1's gradient entirely,
-    # everything upstream by the unit's share).  They are identified BY CONSTRUCTION from the oracle's pre-activations
-    # (|u| <= 2e-6 max|u|: the size of the fp32 accumulation error of a K = H dot product), must be few, and only they get
-    # a different treatment: their rows of linear1's gradient are excluded, and -- only if such a unit exists -- the
-    # other gradients get the bound of one flipped unit (4e-3) instead of 2e-3.
-    kink_units = set()
-    for l, u in enumerate(oaux["ffn_pre"]):
-        near = (u.abs() <= 2e-6 * float(u.abs().max())).reshape(-1, u.shape[-1])
-        kink_units |= {(l, int(j)) for j in near.any(dim=0).nonzero().flatten()}
+    # ReLU units of the decoder FFN on the kink (tests.helpers.ffn_kink_units) must be few, and only they get a different
+    # treatment: their rows of linear1's gradient are excluded, and -- only if such a unit exists -- the other gradients
+    # get the bound of one flipped unit (4e-3) instead of 2e-3.
+    kink_units = ffn_kink_units(oaux["ffn_pre"])
     assert len(kink_units) <= 4, f"H{H}: {len(kink_units)} FFN units on the ReLU kink"
     rtol = 2e-3 if not kink_units else 4e-3
     for n, p in tr.p.items():
         if p.grad is None:
             continue
-        g, r = eng.arena.g(n).cpu(), p.grad
-        for (l, j) in kink_units:
-            if n in (f"transformer.decoder.layers.{l}.linear1.weight", f"transformer.decoder.layers.{l}.linear1.bias"):
-                keep = torch.ones(r.shape[0], dtype=torch.bool)
-                keep[j] = False
-                g, r = g[keep], r[keep]
-            elif n == f"transformer.decoder.layers.{l}.linear2.weight":
-                keep = torch.ones(r.shape[1], dtype=torch.bool)
-                keep[j] = False
-                g, r = g[:, keep], r[:, keep]
+        g, r = without_kink_units(n, eng.arena.g(n).cpu(), p.grad, kink_units)
         close_rel(g, r, f"H{H}/grad {n}" + (f" (kink units {sorted(kink_units)} excluded)" if kink_units else ""), rtol=rtol)
 
 

@@ -130,10 +130,12 @@ def test_pixel_sharded_depth_matches_replicated_two_ranks():
         assert status == "ok", f"rank {rank}: {info}"
 
 
-def _train_worker(rank, world, port, q):
+def _train_worker(rank, world, port, q, shapes=None):
     try:
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+        import datetime
+        # (a bounded wait: ranks that stop agreeing fail this rank with a timeout instead of blocking it in a collective)
+        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
         torch.cuda.set_device(0)
         import tempfile
         from r3d_amd.train_proposed_depth import train
@@ -141,6 +143,10 @@ def _train_worker(rank, world, port, q):
         fx = load_fixture("step_tiny")
         m = fx["meta"]
         batches = [fixture_batch(fx, seed=300 + 10 * s + rank) for s in range(4)]
+        if shapes is not None:                                 # (B, S) per step: the clip length changes from step to step
+            from oracle import synth
+            batches = [[torch.from_numpy(x) for x in synth.make_batch(B, S, m["n_class"], m["pad_idx"], 300 + 10 * i + rank)]
+                       for i, (B, S) in enumerate(shapes)]
         val = [[t[:1] for t in fixture_batch(fx, seed=999)]]
         finals = []
         for graph_steps in (False, True):
@@ -181,6 +187,29 @@ def test_train_loop_graphed_data_parallel_equals_eager_two_ranks():
     res = [q.get(timeout=600) for _ in procs]
     for p in procs:
         p.join(timeout=60)
+    for rank, status, info in res:
+        assert status == "ok", f"rank {rank}: {info}"
+
+
+def test_train_loop_graphed_data_parallel_over_changing_clip_lengths_equals_eager():
+    """The same with the clip length changing between steps, a short shape captured before the longest one appears: a
+    replayed step must clear the pos_embedding gradient rows the longer batch wrote (its graphs are re-captured when the
+    engine's high-water mark of those rows grows), exactly as the step enqueued launch by launch does."""
+    shapes = [(2, 3), (2, 3), (2, 3), (2, 5), (2, 5), (2, 9), (2, 3), (2, 3), (2, 5)]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_train_worker, args=(r, 2, port, q, shapes)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        res = [q.get(timeout=600) for _ in procs]
+    finally:
+        for p in procs:
+            p.join(timeout=60)
+            if p.is_alive():                                   # (never leave a rank holding the GPU)
+                p.terminate()
+                p.join(timeout=30)
     for rank, status, info in res:
         assert status == "ok", f"rank {rank}: {info}"
 
