@@ -453,6 +453,19 @@ int r3d_bn_bwd_apply(const float* rgb, const float* dep, const float* mean, cons
                      const float* gamma_dep, const float* t_drb, const float* t_ddb, const float* dgamma_rgb,
                      const float* dbeta_rgb, const float* dgamma_dep, const float* dbeta_dep, float* d_rgb_pre, float* d_dep,
                      int N, int C, int training, void* stream);
+/* ---- the activation-magnitude token fuser of model/futr_safuser_tokenfusion_vary.py:36-56 -----------------------------
+ * (selection: r3d_colabssum + r3d_token_select with k = C // 4 on the scores mean_(B,T) |x|, in every mode)
+ * r3d_scaled_exchange_fwd : x0 [2N, C] = embd_drop(scaled exchange): selected RGB channels <- alpha * dep, selected depth
+ *                           channels <- alpha * rgb; h1 = norm1(x0), m1 / r1 [2N].
+ * r3d_scaled_exchange_bwd : norm1 backward (+ add1), dropout, exchange adjoint -> d_rgb_pre (with input_embed's ReLU),
+ *                           d_dep, and t_dal [N, C] whose column sum is d alpha; optional norm1 partials ws_n1 [N][2][C]. */
+int r3d_scaled_exchange_fwd(const float* rgb, const float* dep, const float* mask_rgb, const float* mask_dep,
+                            const float* alpha, const uint8_t* drop_mask, float drop_scale, const float* ln1_gamma,
+                            const float* ln1_beta, float* x0, float* h1, float* m1, float* r1, int N, int C, void* stream);
+int r3d_scaled_exchange_bwd(const float* d_h1, const float* x0, const float* m1, const float* r1, const float* ln1_gamma,
+                            const float* add1, const uint8_t* drop_mask, float drop_scale, const float* rgb,
+                            const float* dep, const float* mask_rgb, const float* mask_dep, const float* alpha,
+                            float* d_rgb_pre, float* d_dep, float* t_dal, float* ws_n1, int N, int C, void* stream);
 /* Data-parallel BatchNorm for that fuser (the statistics of the GLOBAL batch, as one process running the reference sees
  * them; replaces what torch.nn.SyncBatchNorm would do for futr_safuser_batchnormalization.py:45-46):
  * r3d_bn_sync_pack     : the local moments left by r3d_bn_stats -> out [4C + 1] = (mean [2][C], M2 = N var [2][C], N);

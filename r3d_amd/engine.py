@@ -28,6 +28,7 @@ DROP_P = 0.1                    # every nn.Dropout on the path (futr_safuser_tok
 
 
 BN_LIVE_PREFIXES = ("fuser.alpha", "fuser.bn_rgb.", "fuser.bn_depth.")    # the BN-blend variant's extra trainable parameters
+VARY_LIVE_PREFIXES = ("fuser.alpha",)                    # the activation-magnitude variant's extra trainable parameter
 
 
 def is_live(name):
@@ -138,6 +139,7 @@ class _Shape:
         if eng.bn:
             self.bn_mean, self.bn_rstd, self.bn_absg = f(2, H), f(2, H), f(2, H)
             self.bn_idx = torch.empty(2, max(1, int(H * 0.1)), dtype=torch.int64, device=dev)     # k = int(0.1 C) (:58)
+        self.no_xres = bool(eng.bn or eng.vary)          # fuser output = norm(Block(x)) without the second x_res add
         self.sums = torch.empty(2, H, dtype=torch.float64, device=dev)
         self.idx = torch.empty(2, H // 4, dtype=torch.int64, device=dev)
         self.mask = f(2, H)
@@ -182,6 +184,8 @@ class _Shape:
             self.d_h2b = f(2 * N, H)                     # second half-K partial of d_h2 (engine.split_k4h)
             if eng.bn:                                   # per-element terms of the BatchNorm / alpha parameter gradients
                 self.bn_terms = [f(N, H) for _ in range(5)]
+            if eng.vary:                                 # per-element terms of the alpha gradient (column sum = d alpha)
+                self.t_dal = f(N, H)
             # dropout keep-masks (one Philox launch fills the whole pool)
             sizes = dict(x0=2 * N * H)
             for l in range(L):
@@ -210,7 +214,12 @@ class FusionEngine:
         # BN-blend fuser variant (model/futr_safuser_batchnormalization.py): BatchNorm on both embeddings, |gamma| scores,
         # alpha blend, no x_res; it takes the composed (un-paired, un-seamed) path around its own seam kernels
         self.bn = hasattr(module.fuser, "bn_rgb")
-        self.arena = ParamArena(list(module.named_parameters()), self.device, BN_LIVE_PREFIXES if self.bn else ())
+        # activation-magnitude fuser variant (model/futr_safuser_tokenfusion_vary.py): scores mean |x| in every mode (a
+        # device-side column reduction each step), alpha-scaled exchange, no x_res; the un-seamed embedding route around
+        # its own seam kernels (csrc/varyfuse.hip), the hidden-128 chains with add_xres = 0
+        self.vary = (not self.bn) and hasattr(module.fuser, "alpha")
+        extra = BN_LIVE_PREFIXES if self.bn else (VARY_LIVE_PREFIXES if self.vary else ())
+        self.arena = ParamArena(list(module.named_parameters()), self.device, extra)
         self.ws = ops.GemmWorkspace(self.device)
         self._sel = {}                                  # constant 0/1 selection matrices of _wgrad_with_sums
         self.ws_side = ops.GemmWorkspace(self.device)
@@ -300,7 +309,7 @@ class FusionEngine:
         # (the fuser MLP's two forward products at hidden >= 512 through the same split-K bf16x3 kernel + reducer: measured
         #  SLOWER -- cfg4's per-GPU shape 1.157 -> 1.236 ms, cfg5's 1.716 -> 1.746: two K-splits of 8 k-steps pay the kernel's
         #  prologue / epilogue twice and the reducer re-reads 16 MB of slabs; they stay on the fp32 64 x 64 tiles)
-        self.use_fused_embed = not self.bn       # train mode: projections' slab sums + LN + exchange + norm1 in one launch
+        self.use_fused_embed = not (self.bn or self.vary)     # train mode: projections' slab sums + LN + exchange + norm1 in one launch
         # False: train()-state steps without dropout (parity runs against a reference whose dropout probabilities were
         # set to 0; RNG streams cannot match).  Read from the module so that it survives model.to() re-creating the engine.
         self.dropout_enabled = bool(getattr(module, "r3d_dropout_enabled", True))
@@ -535,7 +544,7 @@ class FusionEngine:
         # ---- token selection + exchange (:33-66)
         if seam or self.bn:
             pass
-        elif mode == "train":
+        elif mode == "train" and not self.vary:
             idx, mask = self._train_masks(B, S)
         else:
             ops.colabssum(w.rgb, w.sums[0])
@@ -561,6 +570,10 @@ class FusionEngine:
                              a.p("fuser.bn_depth.weight"), a.p("fuser.bn_depth.bias"), a.p("fuser.alpha").view(-1), mask[0],
                              mask[1], dm("x0"), dsc, a.p(pre + "norm1.weight"), a.p(pre + "norm1.bias"), w.x0, w.h1, w.m1,
                              w.r1)
+        elif self.vary:
+            # alpha-scaled exchange + embd_drop + norm1 (futr_safuser_tokenfusion_vary.py:51-56,76; transformerblock.py:122)
+            ops.scaled_exchange_fwd(w.rgb, w.dep, mask[0], mask[1], a.p("fuser.alpha").view(-1), dm("x0"), dsc,
+                                    a.p(pre + "norm1.weight"), a.p(pre + "norm1.bias"), w.x0, w.h1, w.m1, w.r1)
         elif not seam:
             ops.token_exchange_fwd(w.rgb, w.dep, mask[0], mask[1], w.x0, drop_mask=dm("x0"), drop_scale=dsc)
             ops.layernorm_fwd(w.x0, a.p(pre + "norm1.weight"), a.p(pre + "norm1.bias"), w.h1, w.m1, w.r1)
@@ -582,11 +595,11 @@ class FusionEngine:
                      pre_out=w.u, ws=self.ws)
             if gln:
                 ops.gemm_ln_fwd([dict(a=w.f1, w=a.p(pre + "mlp.mlp.2.weight"), bias=a.p(pre + "mlp.mlp.2.bias"), res1=w.x1,
-                                      res2=None if self.bn else w.x0, pre=w.x3, gamma=a.p("fuser.norm.weight"),
+                                      res2=None if w.no_xres else w.x0, pre=w.x3, gamma=a.p("fuser.norm.weight"),
                                       beta=a.p("fuser.norm.bias"), y=w.y, mean=w.mf, rstd=w.rf, pair_out=w.fused)])
             else:
                 ops.gemm(GEMM_NT, w.f1, a.p(pre + "mlp.mlp.2.weight"), w.x3, bias=a.p(pre + "mlp.mlp.2.bias"), res1=w.x1,
-                         res2=None if self.bn else w.x0, ws=self.ws)        # (the BN-blend variant has no x_res, :97,101)
+                         res2=None if w.no_xres else w.x0, ws=self.ws)        # (the BN-blend variant has no x_res, :97,101)
                 ops.layernorm_fwd(w.x3, a.p("fuser.norm.weight"), a.p("fuser.norm.bias"), w.y, w.mf, w.rf,
                                   pair_out=w.fused)
         if not paired:
@@ -798,7 +811,7 @@ class FusionEngine:
                     g1=a.p(pl + "norm1.weight"), be1=a.p(pl + "norm1.bias"), wq=wi[:H], bq=bi[:H],
                     drop_sa=dm("sa_p0"), drop_d1=dm("d1_0"), drop_scale=dsc, sa_qkv=c["sa_qkv"], p_sa=c["p_sa"],
                     sa_o=c["sa_o"], t1_pre=c["t1_pre"], t1=c["t1"], m1=c["m1"], r1=c["r1"], caq=c["caq"],
-                    N=w.N, S=S, K=self.K, H=H, add_xres=0 if self.bn else 1, B=B, Q=Q, heads=heads,
+                    N=w.N, S=S, K=self.K, H=H, add_xres=0 if w.no_xres else 1, B=B, Q=Q, heads=heads,
                     planes={k: pls.ptr(k) for k in pls.keys if not k.endswith("_t") and "dec_" not in k} if pls is not None else None)
             w.tables[key].launch()
             self._erank_fork(w)
@@ -844,13 +857,13 @@ class FusionEngine:
         if gln:      # mlp fc2 + x (+ x_res) -> fuser.norm -> token mean (:92-94), and the decoder's norm1 as a plain job
             ops.gemm_ln_fwd([
                 dict(a=w.f1, w=a.p(pre + "mlp.mlp.2.weight"), bias=a.p(pre + "mlp.mlp.2.bias"), res1=w.x1,
-                     res2=None if self.bn else w.x0, pre=w.x3, gamma=a.p("fuser.norm.weight"),
+                     res2=None if w.no_xres else w.x0, pre=w.x3, gamma=a.p("fuser.norm.weight"),
                      beta=a.p("fuser.norm.bias"), y=w.y, mean=w.mf, rstd=w.rf, pair_out=w.fused),
                 dict(a=None, pre=c["t1_pre"], gamma=a.p(pl + "norm1.weight"), beta=a.p(pl + "norm1.bias"), y=c["t1"],
                      mean=c["m1"], rstd=c["r1"])])
         else:
             ops.gemm(GEMM_NT, w.f1, a.p(pre + "mlp.mlp.2.weight"), w.x3, bias=a.p(pre + "mlp.mlp.2.bias"), res1=w.x1,
-                     res2=None if self.bn else w.x0, ws=self.ws)          # (no x_res in the BN-blend variant)
+                     res2=None if w.no_xres else w.x0, ws=self.ws)          # (no x_res in the BN-blend variant)
             ops.layernorm_fwd_multi([                  # decoder norm1 and the fuser's final norm + token mean: one launch
                 dict(x=c["t1_pre"], gamma=a.p(pl + "norm1.weight"), beta=a.p(pl + "norm1.bias"), y=c["t1"], mean=c["m1"],
                      rstd=c["r1"]),
@@ -1173,9 +1186,16 @@ class FusionEngine:
                                          (t[2], None, 1, a.g("fuser.bn_depth.bias").view(1, H)),
                                          (t[3], None, 1, a.g("fuser.bn_depth.weight").view(1, H)),
                                          (t[4], None, 1, a.g("fuser.alpha").view(1, H))])
+        Jv = Jvc = None
+        if self.vary:                          # norm1's partials: r3d_scaled_exchange_bwd (composed) or the chain, one per
+            Jv = [(w.lnp_seam["n1"], -N, H) + j[3:] if j[0] is w.lnp["n1"] else j for j in J]      # frame; the depth
+            if Jc is not None:                 # LayerNorm's from its own backward launch (row layout)
+                Jvc = [jc if j[0] is not w.lnp["dep"] else j for j, jc in zip(J, Jc)]
         R = [(w.d_fused, None, S, a.g("pos_embedding")[0, :S]),
              (w.d_dep_pre, None, 1, a.g("depth_projection.bias").view(1, H)),
              (w.glayers[self.L - 1]["caqin"], w.glayers[self.L - 1]["sain"], Q, a.g("query_embed.weight"))]
+        if self.vary:                          # d alpha: the column sum of the exchange backward's per-element terms
+            R.append((w.t_dal, None, 1, a.g("fuser.alpha").view(1, H)))
         w.rowsum_group = ops.RowsumGroup(R)
         # The LayerNorm partial sums are column sums as well: when a site's (weight, bias) gradients are adjacent in the
         # arena (they are: same size class, declaration order) its finalize is one more job of the row-sum launch.
@@ -1193,9 +1213,11 @@ class FusionEngine:
                     return None                 # layernorm_bwd wrote the final values itself
             o = (dg.data_ptr() - a.grads.data_ptr()) // 4
             return (part[:blocks * 2 * Hh].view(blocks, 2 * Hh), None, 1, a.grads[o:o + 2 * Hh].view(1, 2 * Hh))
+        w.ln_groups_vary = {n_: ops.LnFinalizeGroup(j_) for n_, j_ in (("vary", Jv), ("vary_chain", Jvc)) if j_ is not None}
         w.tail_groups, w.tail_jobs = {}, {}
         for name, jobs in ((("plain", J), ("seam", Js)) + ((("bn", Jb),) if Jb is not None else ()) +
-                           ((("chain", Jc),) if Jc is not None else ())):
+                           ((("chain", Jc),) if Jc is not None else ()) + ((("vary", Jv),) if Jv is not None else ()) +
+                           ((("vary_chain", Jvc),) if Jvc is not None else ())):
             conv = [as_rowsum(j) for j in jobs]
             if all(c is not None for c in conv):
                 w.tail_groups[name] = ops.RowsumGroup(R + conv)
@@ -1374,12 +1396,20 @@ class FusionEngine:
                     g1d=a.p(pl + "norm1.weight"), drop_d1=dmf("d1_0"), w_out=a.p(pl + "self_attn.out_proj.weight"),
                     sa_qkv=c["sa_qkv"], p_sa=c["p_sa"], drop_sa=dmf("sa_p0"), w_in=a.p(pl + "self_attn.in_proj_weight"),
                     caqin=gl["caqin"], t1pre_out=gl["t1pre"], sap=gl["sap"], sao=gl["sao"], saqkv=gl["saqkv"], sain=gl["sain"],
-                    part_d1=w.chain_parts["d1"], drop_scale=dsc, N=N, S=S, K=K, H=H, add_xres=1, B=B, Q=Q, heads=heads,
+                    part_d1=w.chain_parts["d1"], drop_scale=dsc, N=N, S=S, K=K, H=H, add_xres=0 if w.no_xres else 1, B=B, Q=Q, heads=heads,
                     planes={k: pls.ptr(k) for k in pls.keys if k.endswith("_t") and "dec_" not in k} if pls is not None else None)
             if er:
                 self._erank_join()
                 self._erank_backward(w, ws, dst=w.d_extra)
             w.tables[key].launch()
+            if self.vary:
+                # the chain's own exchange adjoint is the unscaled one: redo the seam from its d_h1 / d_x1 with alpha (its
+                # norm1 partials stand), then the depth LayerNorm + ReLU backward
+                ops.scaled_exchange_bwd(w.d_h1, w.x0, w.m1, w.r1, a.p(pre + "norm1.weight"), w.d_x1, dmf("x0"), dsc, w.rgb,
+                                        w.dep, st["mask"][0], st["mask"][1], a.p("fuser.alpha").view(-1), w.d_rgb_pre,
+                                        w.d_dep, w.t_dal, None)
+                ln_bwd("dep", w.d_dep, w.dep_pre, w.mean_d, w.rstd_d, "depth_layernorm.weight", "depth_layernorm.bias",
+                       w.d_dep_pre, relu=True)
         elif st.get("paired"):
             # the query-side branch (cross-attention query projection, norm1, self-attention: parameter gradients only
             # for a one-layer decoder) and the memory-side chain into the fuser are independent: their GEMMs share launches
@@ -1478,6 +1508,12 @@ class FusionEngine:
             ops.embed_fuse_bwd(w.d_h1, w.x0, w.m1, w.r1, a.p(pre + "norm1.weight"), w.d_x1, w.d_x3, dmf("x0"), dsc, mask[0],
                                mask[1], w.rgb, w.dep_pre, w.mean_d, w.rstd_d, a.p("depth_layernorm.weight"),
                                a.p("depth_layernorm.bias"), w.d_rgb_pre, w.d_dep_pre, w.lnp_seam["n1"], w.lnp_seam["dep"])
+        elif self.vary:                    # norm1 backward + dropout + scaled-exchange adjoint: one launch
+            ops.scaled_exchange_bwd(w.d_h1, w.x0, w.m1, w.r1, a.p(pre + "norm1.weight"), w.d_x1, dmf("x0"), dsc, w.rgb, w.dep,
+                                    mask[0], mask[1], a.p("fuser.alpha").view(-1), w.d_rgb_pre, w.d_dep, w.t_dal,
+                                    w.lnp_seam["n1"])
+            ln_bwd("dep", w.d_dep, w.dep_pre, w.mean_d, w.rstd_d, "depth_layernorm.weight", "depth_layernorm.bias",
+                   w.d_dep_pre, relu=True)
         elif self.bn:
             t = w.bn_terms
             ops.bn_blend_bwd(w.d_h1, w.x0, w.m1, w.r1, a.p(pre + "norm1.weight"), w.d_x1, dmf("x0"), dsc, w.rgb, w.dep,
@@ -1516,7 +1552,10 @@ class FusionEngine:
     def _param_tail(self, w, st, chain):
         """Everything of the backward that only feeds parameter gradients: 2 launches + the broadcast-parameter sums."""
         a, Q = self.arena, self.Q
-        tname = "chain" if chain else ("bn" if self.bn else ("seam" if st["seam"] else "plain"))
+        if self.vary:
+            tname = "vary_chain" if chain else "vary"
+        else:
+            tname = "chain" if chain else ("bn" if self.bn else ("seam" if st["seam"] else "plain"))
         both = self._wgrad_with_sums(w, tname) if (self.fold_rowsums and self.L == 1) else None
         wg = both if both is not None else w.wgrad_group
         wg.set_b(w.rgb_wgrad_idx, st["x_rgb"])
@@ -1529,7 +1568,10 @@ class FusionEngine:
             tail.launch()                  # every LayerNorm parameter gradient: one launch
         else:
             assert not self.bn, "BN-blend variant: LayerNorm gradient slots must be adjacent in the arena"
-            (w.ln_group_seam if st["seam"] else w.ln_group).launch()
+            if self.vary:
+                w.ln_groups_vary[tname].launch()
+            else:
+                (w.ln_group_seam if st["seam"] else w.ln_group).launch()
             w.rowsum_group.launch()
         g_qe = a.g("query_embed.weight")
         for l in reversed(range(self.L - 1)):                       # stacked decoders: remaining layers accumulate

@@ -691,6 +691,38 @@ def bn_blend_bwd(d_h1, x0, m1, r1, ln1_g, add1, drop, drop_scale, rgb, dep, mean
           "r3d_bn_blend_bwd")
 
 
+def _vary_check(N, Cc, rows_n, rows_2n, vecs, drop):
+    for t in rows_n:
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == N * Cc
+    for t, k in rows_2n:
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == k
+    for t in vecs:
+        assert t.is_contiguous() and t.numel() == Cc
+    assert drop is None or (drop.dtype == torch.uint8 and drop.numel() >= 2 * N * Cc)
+
+
+def scaled_exchange_fwd(rgb, dep, m_rgb, m_dep, alpha, drop, drop_scale, ln1_g, ln1_b, x0, h1, m1, r1):
+    """Activation-magnitude fuser seam (csrc/varyfuse.hip): scaled exchange + embd_drop + norm1 -> x0, h1 [2N, C]."""
+    N, Cc = rgb.shape
+    _vary_check(N, Cc, (rgb, dep), ((x0, 2 * N * Cc), (h1, 2 * N * Cc), (m1, 2 * N), (r1, 2 * N)),
+                (m_rgb, m_dep, alpha, ln1_g, ln1_b), drop)
+    check(_lib.load().r3d_scaled_exchange_fwd(_p(rgb), _p(dep), _p(m_rgb), _p(m_dep), _p(alpha), _p(drop), drop_scale,
+                                              _p(ln1_g), _p(ln1_b), _p(x0), _p(h1), _p(m1), _p(r1), N, Cc, _stream()),
+          "r3d_scaled_exchange_fwd")
+
+
+def scaled_exchange_bwd(d_h1, x0, m1, r1, ln1_g, add1, drop, drop_scale, rgb, dep, m_rgb, m_dep, alpha, d_rgb_pre, d_dep,
+                        t_dal, ws_n1=None):
+    """Adjoint of scaled_exchange_fwd: d_rgb_pre (ReLU-gated), d_dep, and t_dal [N, C] whose column sum is d alpha."""
+    N, Cc = rgb.shape
+    big = [(d_h1, 2 * N * Cc), (x0, 2 * N * Cc), (m1, 2 * N), (r1, 2 * N)] + ([(add1, 2 * N * Cc)] if add1 is not None else [])
+    _vary_check(N, Cc, (rgb, dep, d_rgb_pre, d_dep, t_dal), big, (m_rgb, m_dep, alpha, ln1_g), drop)
+    assert ws_n1 is None or ws_n1.numel() >= 2 * N * Cc
+    check(_lib.load().r3d_scaled_exchange_bwd(_p(d_h1), _p(x0), _p(m1), _p(r1), _p(ln1_g), _p(add1), _p(drop), drop_scale,
+                                              _p(rgb), _p(dep), _p(m_rgb), _p(m_dep), _p(alpha), _p(d_rgb_pre), _p(d_dep),
+                                              _p(t_dal), _p(ws_n1), N, Cc, _stream()), "r3d_scaled_exchange_bwd")
+
+
 def bn_bwd_apply(rgb, dep, mean, rstd, g_r, g_d, t_drb, t_ddb, dg_r, db_r, dg_d, db_d, d_rgb_pre, d_dep, training):
     N, Cc = rgb.shape
     check(_lib.load().r3d_bn_bwd_apply(_p(rgb), _p(dep), _p(mean), _p(rstd), _p(g_r), _p(g_d), _p(t_drb), _p(t_ddb), _p(dg_r),

@@ -269,6 +269,9 @@ class DataParallelStep:
         if self.active:
             engine.dur_den = self._den
         self.tp = None
+        if pixel_shard and self.active and getattr(engine, "vary", False):
+            raise NotImplementedError("the activation-magnitude fuser variant (futr_safuser_tokenfusion_vary) runs data "
+                                      "parallel with replicated weights only: no pixel-sharded depth projection")
         if pixel_shard and self.active:
             self.tp = PixelShardedDepth(engine, process_group, equal_batches, input_group)
 
@@ -385,6 +388,9 @@ class RcclStep:
 
     def __init__(self, dp, comm, comm_side, lr, weight_decay, fuse_adam=False):
         self.dp, self.eng, self.tp = dp, dp.eng, dp.tp
+        if getattr(self.eng, "vary", False):
+            raise NotImplementedError("the activation-magnitude fuser variant (futr_safuser_tokenfusion_vary) all-reduces "
+                                      "its selection scores through torch.distributed inside the step; no one-graph RCCL step")
         self.comm, self.side_comm = comm, comm_side
         self.lr, self.wd, self.fuse_adam = lr, weight_decay, fuse_adam and dp.tp is not None
         dev = self.eng.device

@@ -27,7 +27,7 @@ def _unwrap(model):
         m = m.module
     if not isinstance(m, (FUTR, FUTRDepthQuery)):
         raise TypeError("r3d_amd.train_proposed_depth drives r3d_amd.model.futr_safuser_tokenfusion.FUTR (or its "
-                        "BN-blend subclass) and r3d_amd.model.futr_unsupervised_depth.FUTR")
+                        "BN-blend and activation-magnitude subclasses) and r3d_amd.model.futr_unsupervised_depth.FUTR")
     return m
 
 
@@ -375,7 +375,11 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     # one-GPU steps with the fused optimiser replay as hipGraphs (--no_graph_steps / args.graph_steps=False: eager)
     graphed = sharded = None
     rs = None
-    if dp is not None and dp.active and getattr(args, "graph_steps", True) and not getattr(args, "torch_collectives", False):
+    # the activation-magnitude variant all-reduces its selection scores (and their row count, read on the host) inside the
+    # step: with more than one rank its steps run eagerly, without the RCCL one-graph step
+    vary_dp = bool(getattr(eng, "vary", False) and dp is not None and dp.active)
+    if (dp is not None and dp.active and getattr(args, "graph_steps", True) and not getattr(args, "torch_collectives", False)
+            and not vary_dp):
         g0 = optimizer.param_groups[0]
         make_comm = getattr(args, "comm_factory", None)     # (tests: a torch.distributed stand-in for the RCCL binding)
         if make_comm is not None or dist.get_backend() == "nccl":
@@ -390,7 +394,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
             except Exception as e:                  # noqa: BLE001  (no librccl beside torch, communicator refused, ...)
                 print(f"RCCL step unavailable ({type(e).__name__}: {e}); using torch.distributed all-reduces")
                 rs = None
-    if getattr(args, "graph_steps", True) and (dp is None or dp.tp is None):
+    if getattr(args, "graph_steps", True) and (dp is None or dp.tp is None) and not vary_dp:
         graphed = _GraphedSteps(eng, acc_loss, acc_cnt, dp, pad_idx, rs)
     elif rs is not None and dp.tp is not None and isinstance(optimizer, FlatAdamW):
         # --pixel_shard: the sharded one-graph step with a one-batch look-ahead (equal batch shapes on every rank)
