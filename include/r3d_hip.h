@@ -380,6 +380,9 @@ int r3d_mha_core_fwd(const float* q, int ldq, const float* k, int ldk, const flo
 int r3d_mha_core_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* probs,
                      const uint8_t* drop_mask, float drop_scale, const float* d_o, int lddo, float* dq, int lddq, float* dk,
                      int lddk, float* dv, int lddv, int B, int heads, int Lq, int Lk, int dh, void* stream);
+/* 1 if the two calls above run an (Lq, Lk, dh) problem (bwd != 0: r3d_mha_core_bwd), else 0; host-only, the same test
+ * the launches apply: Lq * dh <= 1024 and the core's LDS (score matrix, its gradient, two key chunks) within 160 KiB. */
+int r3d_mha_core_supported(int Lq, int Lk, int dh, int bwd);
 
 /* ---- fused decoder layer, one workgroup per clip (TransformerDecoderLayer.forward_post, model/extras/transformer.py:
  * 281-330; final decoder.norm :182-183; fc|fc_len head futr_safuser_tokenfusion.py:219-226) --------------------------

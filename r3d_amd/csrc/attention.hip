@@ -259,6 +259,14 @@ static size_t mha_lds_bytes(int Lq, int Lk, int dh, bool bwd) {
     return f * sizeof(float);
 }
 
+// The shapes either kernel runs at all: the whole score matrix (and, backward, its gradient) plus two key chunks fit the
+// 160 KiB of LDS one workgroup may declare, and one wave holds the Lq x dh output in 16 slots per lane.
+static bool mha_shape_ok(int Lq, int Lk, int dh, bool bwd) {
+    if (Lq <= 0 || Lk <= 0 || dh <= 0) return false;
+    if ((long)Lq * dh > 1024) return false;                        // 16 output slots per lane
+    return mha_lds_bytes(Lq, Lk, dh, bwd) <= 160 * 1024;
+}
+
 static int mha_check(const MhaArgs& a, bool bwd) {
     if (!a.q || !a.k || !a.v || !a.probs) return R3D_EINVAL;
     if (a.B <= 0 || a.heads <= 0 || a.Lq <= 0 || a.Lk <= 0 || a.dh <= 0) return R3D_EINVAL;
@@ -267,14 +275,19 @@ static int mha_check(const MhaArgs& a, bool bwd) {
     if (!bwd && (!a.o || a.ldo < H)) return R3D_EINVAL;
     if (bwd && (!a.d_o || !a.dq || !a.dk || !a.dv || a.lddo < H || a.lddq < H || a.lddk < H || a.lddv < H))
         return R3D_EINVAL;
-    if (mha_lds_bytes(a.Lq, a.Lk, a.dh, bwd) > 160 * 1024) return R3D_EINVAL;
-    if ((long)a.Lq * a.dh > 1024) return R3D_EINVAL;               // 16 output slots per lane
+    if (!mha_shape_ok(a.Lq, a.Lk, a.dh, bwd)) return R3D_EINVAL;
     return R3D_OK;
 }
 
 }  // namespace r3d
 
 using namespace r3d;
+
+/* 1 if r3d_mha_core_fwd (bwd = 0) / r3d_mha_core_bwd (bwd != 0) runs an (Lq, Lk, dh) problem, else 0: the host admission
+ * predicates (engine.py) ask this before a step enqueues anything, and mha_check applies the same test. */
+R3D_EXPORT int r3d_mha_core_supported(int Lq, int Lk, int dh, int bwd) {
+    return mha_shape_ok(Lq, Lk, dh, bwd != 0) ? 1 : 0;
+}
 
 R3D_EXPORT int r3d_mha_core_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                 const uint8_t* key_padding_mask, const int64_t* key_label, int pad_idx, float* probs,

@@ -59,6 +59,62 @@ def tail_in_decoder_chain(B, H, K, Q):
     return ops.tail_losses_supported(H, K + 1, Q, B * Q)
 
 
+# Shape admission of the engine as a whole (every shape the chains refuse takes the composed launches): checked on the host
+# before anything is enqueued, so a shape past a kernel's limit fails with a ValueError naming that limit instead of an
+# ops.check RuntimeError halfway through a step (or inside a hipGraph capture).  tests/test_width_admission_cpu.py pins them.
+ROW_MAX_H = 2048                # widest instance of the row kernels: layernorm (rowops.hip), decoder tail (tail.hip)
+SEAM_MAX_H = 1024               # the BN-blend and activation-magnitude seams (bnfuse.hip, varyfuse.hip)
+
+
+def check_engine_shape(H, heads, Q, bn=False, vary=False):
+    """Raises ValueError unless the engine runs hidden H with `heads` attention heads and Q queries at some clip length."""
+    if H <= 0 or heads <= 0 or H % 8 or H % heads:
+        raise ValueError(f"hidden {H} with {heads} heads: the engine needs hidden % 8 == 0 and hidden % n_head == 0")
+    if H > ROW_MAX_H:
+        raise ValueError(f"hidden {H} > {ROW_MAX_H}: the widest row kernel (layernorm, decoder tail) instance")
+    if (bn or vary) and H > SEAM_MAX_H:
+        raise ValueError(f"hidden {H} > {SEAM_MAX_H}: the {'BN-blend' if bn else 'activation-magnitude'} fuser's seam "
+                         f"kernels hold a channel row in one wave's registers")
+    dh = H // heads
+    if not ops.mha_core_supported(Q, Q, dh, True):
+        raise ValueError(f"head width {dh} (hidden {H} / {heads} heads) with {Q} queries: the attention core holds "
+                         f"n_query * head width <= 1024 outputs per wave")
+
+
+def check_clip_shape(S, H, heads, Q, max_pos_len, train):
+    """Raises ValueError unless a clip length S runs (train: with the backward, whose attention core needs more LDS)."""
+    if S <= 0:
+        raise ValueError(f"clip length {S}: at least one frame")
+    if S > max_pos_len:
+        raise ValueError(f"clip length {S} > max_pos_len {max_pos_len}: the rows of pos_embedding")
+    dh = H // heads
+    if not ops.mha_core_supported(Q, S, dh, train):
+        raise ValueError(f"clip length {S} at head width {dh}: the cross-attention core's {'backward' if train else 'forward'} "
+                         f"keeps {Q} x {S} scores in LDS, past its 160 KiB")
+
+
+def check_erank_shape(B, S, H):
+    """Raises ValueError unless the rank penalty's Jacobi runs on the [B*S, H] fused tokens: in one CU's LDS, or blocked
+    on the orientation with the fewer columns (columns of max(B*S, H) rows, two blocks of them in LDS)."""
+    N = B * S
+    if ops.erank_fits(N, H) or ops.erank_blocked_supported(max(N, H), min(N, H)):
+        return
+    raise ValueError(f"{B} clips x {S} frames at hidden {H} with the rank penalty: the blocked Jacobi holds two blocks of "
+                     f"{max(N, H)}-long columns in LDS, past its 150 KiB")
+
+
+def max_clip_len(H, heads, Q, max_pos_len, train):
+    """The longest clip check_clip_shape admits (the LDS bound grows monotonically with S)."""
+    lo, hi = 0, max_pos_len
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if ops.mha_core_supported(Q, mid, H // heads, train):
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
 class ParamArena:
     """Flat arenas; live parameters first (AdamW touches only that prefix), depth_projection.weight last among them
     so that everything else forms one contiguous all-reduce bucket that is ready before the big weight gradient."""
@@ -210,7 +266,6 @@ class FusionEngine:
         self.dh = self.H // self.heads
         self.pad_idx = module.src_pad_idx
         self.P, self.D = module.depth_projection.in_features, module.input_embed.in_features
-        assert self.H % 8 == 0 and self.H % self.heads == 0
         # BN-blend fuser variant (model/futr_safuser_batchnormalization.py): BatchNorm on both embeddings, |gamma| scores,
         # alpha blend, no x_res; it takes the composed (un-paired, un-seamed) path around its own seam kernels
         self.bn = hasattr(module.fuser, "bn_rgb")
@@ -218,6 +273,8 @@ class FusionEngine:
         # device-side column reduction each step), alpha-scaled exchange, no x_res; the un-seamed embedding route around
         # its own seam kernels (csrc/varyfuse.hip), the hidden-128 chains with add_xres = 0
         self.vary = (not self.bn) and hasattr(module.fuser, "alpha")
+        check_engine_shape(self.H, self.heads, self.Q, self.bn, self.vary)
+        self.max_pos_len = module.pos_embedding.shape[1]
         extra = BN_LIVE_PREFIXES if self.bn else (VARY_LIVE_PREFIXES if self.vary else ())
         self.arena = ParamArena(list(module.named_parameters()), self.device, extra)
         self.ws = ops.GemmWorkspace(self.device)
@@ -363,6 +420,7 @@ class FusionEngine:
     def _shape(self, B, S, train):
         key = (B, S, bool(train))
         if key not in self.shapes:
+            check_clip_shape(S, self.H, self.heads, self.Q, self.max_pos_len, train)    # (before anything is enqueued)
             self.shapes[key] = _Shape(self, B, S, train)
         return self.shapes[key]
 
@@ -400,6 +458,8 @@ class FusionEngine:
         x_dep = depth.reshape(N, -1)
         assert x_rgb.shape[1] == self.D and x_dep.shape[1] == self.P, (x_rgb.shape, x_dep.shape, self.D, self.P)
         assert x_rgb.is_contiguous() and x_dep.is_contiguous()
+        if need_grad and self.erank_weight != 0.0:
+            check_erank_shape(B, S, self.H)      # (before anything is enqueued, as _shape's own checks)
         w = self._shape(B, S, need_grad)
         self._loss_pending = None          # (see losses(): a pending loss reduction never survives into another step)
         self._erank_join()                 # (a forward whose backward never ran: its sweep still reads the workspace)
@@ -1581,9 +1641,12 @@ class FusionEngine:
 
     # ------------------------------------------------------------------------------------------------------
     def set_lr(self, lr):
+        """True when it enqueued a new value (on the current stream)."""
         if self._lr_host != float(lr):          # lr lives in device memory so a captured graph sees scheduler updates
             self.lr_t.fill_(float(lr))
             self._lr_host = float(lr)
+            return True
+        return False
 
     def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
               skip_depth=False, prefill_dropout=False, before_flat=None):
@@ -1595,13 +1658,16 @@ class FusionEngine:
         prefill_dropout: the same launch also fills the dropout pool of the step's workspace with the NEXT step's masks
         (valid while the next forward uses the same shape and the dropout offset is not advanced again)."""
         a = self.arena
-        self.set_lr(lr)
+        filled = self.set_lr(lr)
         kw = dict(beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
         n0 = 0
         if self._tail_pending and ticked and self.tp is None and not skip_depth and before_flat is None:
             # the branch that produced the small bucket's gradients goes on to update it; this stream keeps the one weight
             # whose gradient it has just written (AdamW is element-wise: the cut changes no bit)
             n0 = a.bucket_small[1]
+            if filled:                          # the branch last waited on this stream before the fill: order it first
+                                                # (train_step and train() set lr before the step: no join there)
+                self.side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self.side):
                 ops.adamw_flat(a.params[:n0], a.grads[:n0], a.exp_avg[:n0], a.exp_avg_sq[:n0], self.lr_t, self.step_t, **kw)
         else:
@@ -1634,6 +1700,7 @@ class FusionEngine:
 
     def train_step(self, feats, depth, past_label, target_dur, target, lr, weight_decay, training=True):
         """forward + losses + backward + AdamW, all enqueued, no host sync.  Returns (loss[4], counts[4]) on device."""
+        self.set_lr(lr)             # in front of the step: the parameter-gradient branch then sees it without a join
         keep, self.defer_tail = self.defer_tail, True       # forward -> losses -> backward back to back: one tail launch
         keep_r, self.defer_loss_reduce = self.defer_loss_reduce, True     # loss statistics reduced in the AdamW launch
         try:

@@ -630,6 +630,11 @@ def token_exchange_bwd(dx0, rgb, mask_rgb, mask_dep, d_rgb_pre, d_dep, *, drop_m
 # ----------------------------------------------------------------------------------------------------------
 # attention core
 # ----------------------------------------------------------------------------------------------------------
+def mha_core_supported(Lq, Lk, dh, bwd):
+    """mha_core_fwd (bwd False) / mha_core_bwd (bwd True) runs an (Lq, Lk, dh) problem: the launches' own check."""
+    return bool(_lib.load().r3d_mha_core_supported(Lq, Lk, dh, 1 if bwd else 0))
+
+
 def mha_core_fwd(q, k, v, probs, o, B, heads, Lq, Lk, dh, *, kpm=None, key_labels=None, pad_idx=0, drop_mask=None,
                  drop_scale=1.0):
     lib = _lib.load()
@@ -915,6 +920,13 @@ def dropout_mask(mask, p, seed, offset_t=None):
 
 def erank_fits(R, Cc):
     return _lib.load().r3d_erank_lds_bytes(R, Cc) <= 160 * 1024 - 256
+
+
+def erank_blocked_supported(R, Cc):
+    """r3d_erank_blocked runs an [R, C] matrix: two blocks of R-long columns fit one CU's LDS (host-only, no launch)."""
+    import ctypes
+    sz = (ctypes.c_int64 * 4)()
+    return _lib.load().r3d_erank_blocked_sizes(R, Cc, 16, ctypes.cast(sz, ctypes.c_void_p)) == 0
 
 
 def erank_jacobi(x, sigma, stats, *, af_t=None, gram=False, max_sweeps=30):

@@ -107,9 +107,9 @@ def ref_losses(out, lab, dur, tgt, pad_idx):
                 seg_correct=sc, seg_total=st, act_correct=ac, act_total=at)
 
 
-def case_step(tag, H, B, S, n_class, n_dec, seed, lr=1e-3, wd=5e-3, with_step=True, zero_mean_depth=False):
+def case_step(tag, H, B, S, n_class, n_dec, seed, lr=1e-3, wd=5e-3, with_step=True, zero_mean_depth=False, n_head=8):
     """forward (eval state, mode='train') + losses + backward + one AdamW step on the reference."""
-    model, args, pad_idx, names_shapes = build_reference(H, n_class, n_dec)
+    model, args, pad_idx, names_shapes = build_reference(H, n_class, n_dec, n_head=n_head)
     model.eval()
     batch = t_batch(synth.make_batch(B, S, n_class, pad_idx, seed, zero_mean_depth=zero_mean_depth))
     feats, depth, lab, dur, tgt = batch
@@ -134,7 +134,7 @@ def case_step(tag, H, B, S, n_class, n_dec, seed, lr=1e-3, wd=5e-3, with_step=Tr
     fused = fused_holder["fused"].detach()
     fx = {
         "meta": json.dumps(dict(tag=tag, H=H, B=B, S=S, n_class=n_class, pad_idx=pad_idx, n_dec=n_dec, seed=seed,
-                                n_head=8, n_query=8, mode="train", lr=lr, wd=wd,
+                                n_head=n_head, n_query=8, mode="train", lr=lr, wd=wd,
                                 zero_mean_depth=zero_mean_depth, torch=torch.__version__)),
         "param_names": json.dumps([n for n, _ in names_shapes]),
         "param_shapes": json.dumps([list(s) for _, s in names_shapes]),
@@ -160,7 +160,7 @@ def case_step(tag, H, B, S, n_class, n_dec, seed, lr=1e-3, wd=5e-3, with_step=Tr
 
     # ---- oracle cross-check (forward, losses, grads) ---------------------------------------------------
     p0 = {n: torch.from_numpy(synth.fill_value(n, s, j)) for j, (n, s) in enumerate(names_shapes)}
-    tr = O.CpuTrainer(p0, pad_idx, n_head=8, n_layers=n_dec, lr=lr, wd=wd)
+    tr = O.CpuTrainer(p0, pad_idx, n_head=n_head, n_layers=n_dec, lr=lr, wd=wd)
     ores, oout, oaux = tr.step(batch, apply=False)
     for k in ("action", "duration", "seg"):
         check_close(f"{tag}/out/{k}", oout[k], out[k])
@@ -340,6 +340,7 @@ if __name__ == "__main__":
     case_step("step_cfg2", H=128, B=8, S=16, n_class=17, n_dec=1, seed=1)
     case_step("step_cfg2_zm", H=128, B=8, S=16, n_class=17, n_dec=1, seed=10, zero_mean_depth=True)
     case_step("step_k122_dec2", H=64, B=3, S=7, n_class=122, n_dec=2, seed=13452)
+    case_step("step_h136_4h", H=136, B=4, S=12, n_class=19, n_dec=1, seed=136, n_head=4)   # off the 64-column grid, dh 34
     case_val("val_h128", H=128, S=11, n_class=17, n_dec=1, seed=10)
     case_val("val_h64", H=64, S=23, n_class=17, n_dec=1, seed=1)
     case_train_loop("train_loop", H=64, B=8, S=6, n_class=17, n_steps=2, seed=1)

@@ -37,7 +37,7 @@ def close_rel(a, b, what, rtol=RTOL):
     assert err <= rtol * scale, f"{what}: max abs err {err:.3e} vs scale {scale:.3e} (rel {err / scale:.2e})"
 
 
-@pytest.mark.parametrize("tag", ["step_tiny", "step_cfg2", "step_cfg2_zm", "step_k122_dec2"])
+@pytest.mark.parametrize("tag", ["step_tiny", "step_cfg2", "step_cfg2_zm", "step_k122_dec2", "step_h136_4h"])
 def test_step_parity(tag, oracle_lib):
     fx = load_fixture(tag)
     m = fx["meta"]

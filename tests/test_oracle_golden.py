@@ -18,7 +18,7 @@ def check_stats(got, ref, rtol=1e-4):
     assert bool((np.abs(got[:, 3:] - ref[:, 3:]) <= 10 * rtol * scale + 1e-7).all()), "samples"
 
 
-STEP_CASES = ["step_tiny", "step_cfg2", "step_cfg2_zm", "step_k122_dec2"]
+STEP_CASES = ["step_tiny", "step_cfg2", "step_cfg2_zm", "step_k122_dec2", "step_h136_4h"]
 
 
 @pytest.mark.parametrize("tag", STEP_CASES)
