@@ -436,12 +436,14 @@ def forward_unsup_depth(p, inputs, depth, mode, pad_idx, n_head=8, n_layers=1, n
     d = F.linear(d, p["depth_projection.weight"], p["depth_projection.bias"])        # :109
     d = F.relu(layer_norm(d, p["depth_layernorm.weight"], p["depth_layernorm.bias"]))  # :110-111
     query = d + pe                                                                   # :115 (pos_enc_depth)
-    tgt = decoder(p, mem, pos, query, kpm, n_head, n_layers)                         # :128, tgt = zeros_like(query) :126
+    aux = {}
+    tgt = decoder(p, mem, pos, query, kpm, n_head, n_layers, capture=aux)            # :128, tgt = zeros_like(query) :126
     pooled = F.adaptive_avg_pool1d(tgt.permute(0, 2, 1), n_query).permute(0, 2, 1)   # :134
     out = {"action": F.linear(pooled, p["fc.weight"], p["fc.bias"]),                  # :140-144
            "duration": F.linear(pooled, p["fc_len.weight"], p["fc_len.bias"]).squeeze(2),
            "seg": F.linear(mem, p["fc_seg.weight"], p["fc_seg.bias"])}               # :148 (src returned unchanged = memory)
-    return out, dict(memory=mem, query=query, tgt=tgt, pooled=pooled)
+    aux.update(memory=mem, query=query, tgt=tgt, pooled=pooled)
+    return out, aux
 
 
 def forward_proposed(p, inputs, query, mode, pad_idx, n_head=8, n_layers=1, n_query=8):
@@ -459,12 +461,14 @@ def forward_proposed(p, inputs, query, mode, pad_idx, n_head=8, n_layers=1, n_qu
     mem = F.relu(F.linear(src, p["input_embed.weight"], p["input_embed.bias"]))
     q = F.embedding(query.long(), p["query_embed.weight"]) + sinusoid_table(S, H)     # positional_embedding_l3[:S] (:63-69,104-106)
     pos = p["pos_embedding"][:, :S]
-    tgt = decoder(p, mem, pos, q, kpm, n_head, n_layers)
+    aux = {}
+    tgt = decoder(p, mem, pos, q, kpm, n_head, n_layers, capture=aux)
     pooled = F.adaptive_avg_pool1d(tgt.permute(0, 2, 1), n_query).permute(0, 2, 1)
     out = {"action": F.linear(pooled, p["fc.weight"], p["fc.bias"]),
            "duration": F.linear(pooled, p["fc_len.weight"], p["fc_len.bias"]).squeeze(2),
            "seg": F.linear(mem, p["fc_seg.weight"], p["fc_seg.bias"])}
-    return out, dict(memory=mem, query=q, tgt=tgt, pooled=pooled)
+    aux.update(memory=mem, query=q, tgt=tgt, pooled=pooled)
+    return out, aux
 
 
 UNSUP_LIVE_PREFIXES = ("input_embed.", "depth_projection.", "depth_layernorm.", "pos_embedding", "transformer.decoder.",

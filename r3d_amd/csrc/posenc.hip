@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restric
 }
 
 // Label-index queries of model/futr_proposed.py:103-106: out[r, :] = weight[idx[r], :] + table[r % S, :] (nn.Embedding lookup +
-// the sinusoidal table), and the lookup's adjoint d_weight[e, :] = sum over rows with idx[r] == e of d_out[r, :] -- one
+// the sinusoidal table), and the lookup's adjoint d_weight[e, :] = sum over rows with clamp(idx[r]) == e of d_out[r, :] -- one
 // workgroup per embedding row scanning the (few hundred) indices: deterministic, no atomics.
 __global__ __launch_bounds__(256) void embed_gather_fwd_kernel(const float* __restrict__ weight, int n_embed, const int64_t* __restrict__ idx,
                                                                const float* __restrict__ table, int ldt, int S, float* __restrict__ out,
@@ -84,13 +84,17 @@ __global__ __launch_bounds__(256) void embed_gather_fwd_kernel(const float* __re
     }
 }
 
+// (the forward's clamp applied to every index: a row the forward read for an out-of-range index receives its gradient)
 __global__ __launch_bounds__(256) void embed_gather_bwd_kernel(const float* __restrict__ d_out, int ldd, const int64_t* __restrict__ idx,
-                                                               float* __restrict__ d_weight, int rows, int H) {
+                                                               float* __restrict__ d_weight, int n_embed, int rows, int H) {
     const int e = blockIdx.x;
     for (int c = threadIdx.x; c < H; c += 256) {
         float acc = 0.f;
-        for (int r = 0; r < rows; ++r)
-            if (idx[r] == (int64_t)e) acc += d_out[(size_t)r * ldd + c];
+        for (int r = 0; r < rows; ++r) {
+            int64_t i = idx[r];
+            i = i < 0 ? 0 : (i >= n_embed ? n_embed - 1 : i);
+            if (i == (int64_t)e) acc += d_out[(size_t)r * ldd + c];
+        }
         d_weight[(size_t)e * H + c] = acc;
     }
 }
@@ -150,11 +154,13 @@ R3D_EXPORT int r3d_embed_gather_fwd(const float* weight, int n_embed, const int6
     return R3D_OK;
 }
 
-/* d_weight[e, :] = sum_{r : idx[r] == e} d_out[r, :]  for every embedding row e (rows never looked up get zeros). */
+/* d_weight[e, :] = sum_{r : clamp(idx[r]) == e} d_out[r, :]  for every embedding row e (rows never looked up get zeros): the
+ * adjoint of r3d_embed_gather_fwd, whose clamp into [0, n_embed) it applies too. */
 R3D_EXPORT int r3d_embed_gather_bwd(const float* d_out, int ldd, const int64_t* idx, float* d_weight, int n_embed, int rows,
                                     int H, void* stream) {
     R3D_REQUIRE(d_out && idx && d_weight && n_embed > 0 && rows > 0 && H > 0 && ldd >= H);
-    hipLaunchKernelGGL(embed_gather_bwd_kernel, dim3(n_embed), dim3(256), 0, (hipStream_t)stream, d_out, ldd, idx, d_weight, rows, H);
+    hipLaunchKernelGGL(embed_gather_bwd_kernel, dim3(n_embed), dim3(256), 0, (hipStream_t)stream, d_out, ldd, idx, d_weight, n_embed, rows,
+                       H);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }

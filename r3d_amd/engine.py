@@ -66,12 +66,17 @@ ROW_MAX_H = 2048                # widest instance of the row kernels: layernorm 
 SEAM_MAX_H = 1024               # the BN-blend and activation-magnitude seams (bnfuse.hip, varyfuse.hip)
 
 
-def check_engine_shape(H, heads, Q, bn=False, vary=False):
-    """Raises ValueError unless the engine runs hidden H with `heads` attention heads and Q queries at some clip length."""
+def check_hidden(H, heads):
+    """Raises ValueError unless the row kernels and the head split take hidden H with `heads` attention heads."""
     if H <= 0 or heads <= 0 or H % 8 or H % heads:
         raise ValueError(f"hidden {H} with {heads} heads: the engine needs hidden % 8 == 0 and hidden % n_head == 0")
     if H > ROW_MAX_H:
         raise ValueError(f"hidden {H} > {ROW_MAX_H}: the widest row kernel (layernorm, decoder tail) instance")
+
+
+def check_engine_shape(H, heads, Q, bn=False, vary=False):
+    """Raises ValueError unless the engine runs hidden H with `heads` attention heads and Q queries at some clip length."""
+    check_hidden(H, heads)
     if (bn or vary) and H > SEAM_MAX_H:
         raise ValueError(f"hidden {H} > {SEAM_MAX_H}: the {'BN-blend' if bn else 'activation-magnitude'} fuser's seam "
                          f"kernels hold a channel row in one wave's registers")

@@ -17,7 +17,46 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .engine import ParamArena, DROP_P, EXCLUDE_CLASS_IDX
+from .engine import ParamArena, DROP_P, EXCLUDE_CLASS_IDX, check_hidden
+
+
+# Shape admission (as engine.py's): every clip brings S queries, so both decoder attentions run Lq = Lk = S and the core's
+# limits (S * head width <= 1024 outputs per wave, S x S scores in 160 KiB of LDS) bound the clip length itself.  Checked on
+# the host before anything is enqueued; tests/test_query_admission_cpu.py pins them.
+def check_query_engine_shape(H, heads):
+    """Raises ValueError unless the engine runs hidden H with `heads` attention heads at some training clip length."""
+    check_hidden(H, heads)
+    dh = H // heads
+    if not ops.mha_core_supported(1, 1, dh, True):                # (the bound only tightens as S grows)
+        raise ValueError(f"head width {dh} (hidden {H} / {heads} heads): no clip length trains -- the attention core's "
+                         f"backward needs S * head width <= 1024 outputs per wave and its key chunks in 160 KiB of LDS")
+
+
+def check_query_clip_shape(S, H, heads, max_pos_len, train):
+    """Raises ValueError unless a clip of S frames runs (train: with the backward, whose attention core needs more LDS).
+    max_pos_len: the rows of pos_embedding (and, label-query, of positional_embedding_l3)."""
+    if S <= 0:
+        raise ValueError(f"clip length {S}: at least one frame")
+    if S > max_pos_len:
+        raise ValueError(f"clip length {S} > max_pos_len {max_pos_len}: the rows of the positional tables")
+    dh = H // heads
+    if not ops.mha_core_supported(S, S, dh, train):
+        raise ValueError(f"clip length {S} at head width {dh}: the decoder's attention cores run {S} queries x {S} keys, past "
+                         f"the {'backward' if train else 'forward'} core's S * head width <= 1024 outputs per wave or its "
+                         f"S x S scores in 160 KiB of LDS")
+
+
+def max_query_clip_len(H, heads, max_pos_len, train):
+    """The longest clip check_query_clip_shape admits (0: none; the bound tightens monotonically with S)."""
+    lo, hi = 0, max_pos_len
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if ops.mha_core_supported(mid, mid, H // heads, train):
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
 
 LIVE_PREFIXES = ("input_embed.", "depth_projection.", "depth_layernorm.", "pos_embedding", "transformer.decoder.",
                  "fc_seg.", "fc.", "fc_len.", "query_embed.")     # (query_embed: the label-query variant, model/futr_proposed.py)
@@ -80,6 +119,7 @@ class UnsupDepthEngine:
         ops._lib.load()
         self.H, self.Q, self.K = module.hidden_dim, module.n_query, module.n_class
         self.heads, self.L = module.n_head, module.num_decoder_layers
+        check_query_engine_shape(self.H, self.heads)
         self.dh = self.H // self.heads
         self.pad_idx = module.src_pad_idx
         # label_query: model/futr_proposed.py -- the decoder query is nn.Embedding(label indices) + a sinusoidal table
@@ -88,11 +128,11 @@ class UnsupDepthEngine:
         self.D = module.input_embed.in_features
         self.P = None if self.label_query else module.depth_projection.in_features
         self.Kseg = module.fc_seg.out_features
-        assert self.H % 8 == 0 and self.H % self.heads == 0
         self.arena = _Arena(list(module.named_parameters()), self.device)
         self.pe = module.pos_enc.pos_table[0]                     # [3000, H] sinusoid buffer (position.py:19-27)
         self.pe_depth = None if self.label_query else module.pos_enc_depth.pos_table[0]
         self.pe_l3 = module.positional_embedding_l3.to(self.device).contiguous() if self.label_query else None
+        self.max_pos_len = min(t.shape[0] for t in (module.pos_embedding[0], self.pe, self.pe_depth, self.pe_l3) if t is not None)
         self.ws = ops.GemmWorkspace(self.device)
         self.dropout_enabled = bool(getattr(module, "r3d_dropout_enabled", True))
         self.erank_weight = 0.0                # (the rank penalty is defined on the fuser's tokens; this model has no fuser)
@@ -121,6 +161,7 @@ class UnsupDepthEngine:
     def _shape(self, B, S, train):
         key = (B, S, bool(train))
         if key not in self.shapes:
+            check_query_clip_shape(S, self.H, self.heads, self.max_pos_len, train)     # (before anything is enqueued)
             self.shapes[key] = _Shape(self, B, S, train)
         return self.shapes[key]
 
