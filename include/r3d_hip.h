@@ -456,6 +456,25 @@ int r3d_bn_bwd_apply(const float* rgb, const float* dep, const float* mean, cons
                      const float* gamma_dep, const float* t_drb, const float* t_ddb, const float* dgamma_rgb,
                      const float* dbeta_rgb, const float* dgamma_dep, const float* dbeta_dep, float* d_rgb_pre, float* d_dep,
                      int N, int C, int training, void* stream);
+/* ---- the plain SA-Fuser of model/futr_safuser_depth.py:36-62 (no selection, no exchange, no x_res) ---------------------------
+ * r3d_plain_fuse_fwd : r3d_embed_fuse_fwd with x0 [2N, H] = embd_drop([rgb; dep] + tok) (tok = fuser.modality_token [H])
+ *                      in place of the exchange; jobs_device / njobs / total_blocks (optional, NULL = none) as
+ *                      r3d_embed_fuse_fwd_planes.
+ * r3d_plain_fuse_bwd : norm1 backward (+ add1), dropout -> d_rgb_pre (with input_embed's ReLU), d_dep_pre (depth LayerNorm
+ *                      + ReLU backward), the per-frame partials ws_n1 / ws_dep [N][2][H], and t_tok [N, H] = the sum of each
+ *                      frame's two post-dropout row gradients (column sum = d modality_token).  d_rgb_pre, d_dep_pre, ws_n1,
+ *                      ws_dep: all given, or all NULL for t_tok alone. */
+int r3d_plain_fuse_fwd(const float* rgb_src, int ns_r, const float* bias_r, const float* dep_src, int ns_d,
+                       const float* bias_d, const float* lnd_gamma, const float* lnd_beta, const float* tok,
+                       const uint8_t* drop_mask, float drop_scale, const float* ln1_gamma, const float* ln1_beta,
+                       float* rgb_out, float* dep_pre_out, float* mean_d, float* rstd_d, float* dep_out, float* x0,
+                       float* h1, float* m1, float* r1, int N, int H, const r3d_plane_job* jobs_device, int njobs,
+                       int total_blocks, void* stream);
+int r3d_plain_fuse_bwd(const float* d_h1, const float* x0, const float* m1, const float* r1, const float* ln1_gamma,
+                       const float* add1, const uint8_t* drop_mask, float drop_scale, const float* rgb,
+                       const float* dep_pre, const float* mean_d, const float* rstd_d, const float* lnd_gamma,
+                       const float* lnd_beta, float* d_rgb_pre, float* d_dep_pre, float* ws_n1, float* ws_dep,
+                       float* t_tok, int N, int H, void* stream);
 /* ---- the activation-magnitude token fuser of model/futr_safuser_tokenfusion_vary.py:36-56 -----------------------------
  * (selection: r3d_colabssum + r3d_token_select with k = C // 4 on the scores mean_(B,T) |x|, in every mode)
  * r3d_scaled_exchange_fwd : x0 [2N, C] = embd_drop(scaled exchange): selected RGB channels <- alpha * dep, selected depth

@@ -229,6 +229,8 @@ _SIGNATURES = {
     "r3d_bn_blend_fwd": ([_P] * 12 + [_F] + [_P] * 6 + [_I, _I, _P], C.c_int),
     "r3d_bn_blend_bwd": ([_P] * 7 + [_F] + [_P] * 17 + [_I, _I, _P], C.c_int),
     "r3d_bn_bwd_apply": ([_P] * 14 + [_I, _I, _I, _P], C.c_int),
+    "r3d_plain_fuse_fwd": ([_P, _I, _P, _P, _I] + [_P] * 5 + [_F] + [_P] * 11 + [_I, _I, _P, _I, _I, _P], C.c_int),
+    "r3d_plain_fuse_bwd": ([_P] * 7 + [_F] + [_P] * 11 + [_I, _I, _P], C.c_int),
     "r3d_scaled_exchange_fwd": ([_P] * 6 + [_F] + [_P] * 6 + [_I, _I, _P], C.c_int),
     "r3d_scaled_exchange_bwd": ([_P] * 7 + [_F] + [_P] * 9 + [_I, _I, _P], C.c_int),
     "r3d_bn_sync_pack": ([_P, _P, _I, _I, _P, _P], C.c_int),

@@ -29,6 +29,7 @@ DROP_P = 0.1                    # every nn.Dropout on the path (futr_safuser_tok
 
 BN_LIVE_PREFIXES = ("fuser.alpha", "fuser.bn_rgb.", "fuser.bn_depth.")    # the BN-blend variant's extra trainable parameters
 VARY_LIVE_PREFIXES = ("fuser.alpha",)                    # the activation-magnitude variant's extra trainable parameter
+PLAIN_LIVE_PREFIXES = ("fuser.modality_token",)          # the plain SA-Fuser's token, added to both tokens of every frame
 
 
 def is_live(name):
@@ -63,7 +64,7 @@ def tail_in_decoder_chain(B, H, K, Q):
 # before anything is enqueued, so a shape past a kernel's limit fails with a ValueError naming that limit instead of an
 # ops.check RuntimeError halfway through a step (or inside a hipGraph capture).  tests/test_width_admission_cpu.py pins them.
 ROW_MAX_H = 2048                # widest instance of the row kernels: layernorm (rowops.hip), decoder tail (tail.hip)
-SEAM_MAX_H = 1024               # the BN-blend and activation-magnitude seams (bnfuse.hip, varyfuse.hip)
+SEAM_MAX_H = 1024               # the BN-blend, activation-magnitude and plain seams (bnfuse.hip, varyfuse.hip, plainfuse.hip)
 
 
 def check_hidden(H, heads):
@@ -74,12 +75,12 @@ def check_hidden(H, heads):
         raise ValueError(f"hidden {H} > {ROW_MAX_H}: the widest row kernel (layernorm, decoder tail) instance")
 
 
-def check_engine_shape(H, heads, Q, bn=False, vary=False):
+def check_engine_shape(H, heads, Q, bn=False, vary=False, plain=False):
     """Raises ValueError unless the engine runs hidden H with `heads` attention heads and Q queries at some clip length."""
     check_hidden(H, heads)
-    if (bn or vary) and H > SEAM_MAX_H:
-        raise ValueError(f"hidden {H} > {SEAM_MAX_H}: the {'BN-blend' if bn else 'activation-magnitude'} fuser's seam "
-                         f"kernels hold a channel row in one wave's registers")
+    if (bn or vary or plain) and H > SEAM_MAX_H:
+        kind = "BN-blend fuser" if bn else ("activation-magnitude fuser" if vary else "plain SA-Fuser")
+        raise ValueError(f"hidden {H} > {SEAM_MAX_H}: the {kind}'s seam kernels hold a channel row in one wave's registers")
     dh = H // heads
     if not ops.mha_core_supported(Q, Q, dh, True):
         raise ValueError(f"head width {dh} (hidden {H} / {heads} heads) with {Q} queries: the attention core holds "
@@ -200,7 +201,7 @@ class _Shape:
         if eng.bn:
             self.bn_mean, self.bn_rstd, self.bn_absg = f(2, H), f(2, H), f(2, H)
             self.bn_idx = torch.empty(2, max(1, int(H * 0.1)), dtype=torch.int64, device=dev)     # k = int(0.1 C) (:58)
-        self.no_xres = bool(eng.bn or eng.vary)          # fuser output = norm(Block(x)) without the second x_res add
+        self.no_xres = bool(eng.bn or eng.vary or eng.plain)     # fuser output = norm(Block(x)) without the second x_res add
         self.sums = torch.empty(2, H, dtype=torch.float64, device=dev)
         self.idx = torch.empty(2, H // 4, dtype=torch.int64, device=dev)
         self.mask = f(2, H)
@@ -247,6 +248,8 @@ class _Shape:
                 self.bn_terms = [f(N, H) for _ in range(5)]
             if eng.vary:                                 # per-element terms of the alpha gradient (column sum = d alpha)
                 self.t_dal = f(N, H)
+            if eng.plain:                                # per-frame modality-token partials (column sum = d modality_token)
+                self.t_tok = f(N, H)
             # dropout keep-masks (one Philox launch fills the whole pool)
             sizes = dict(x0=2 * N * H)
             for l in range(L):
@@ -278,9 +281,14 @@ class FusionEngine:
         # device-side column reduction each step), alpha-scaled exchange, no x_res; the un-seamed embedding route around
         # its own seam kernels (csrc/varyfuse.hip), the hidden-128 chains with add_xres = 0
         self.vary = (not self.bn) and hasattr(module.fuser, "alpha")
-        check_engine_shape(self.H, self.heads, self.Q, self.bn, self.vary)
+        # plain SA-Fuser (model/futr_safuser_depth.py), marked on its fuser class: no selection or exchange, the live
+        # modality token added to both tokens in the embedding seam (csrc/plainfuse.hip), no x_res; the seam in every mode,
+        # the hidden-128 chains with all-zero exchange masks (the identity adjoint) and add_xres = 0
+        self.plain = getattr(type(module.fuser), "r3d_fuser_kind", None) == "plain"
+        check_engine_shape(self.H, self.heads, self.Q, self.bn, self.vary, self.plain)
         self.max_pos_len = module.pos_embedding.shape[1]
-        extra = BN_LIVE_PREFIXES if self.bn else (VARY_LIVE_PREFIXES if self.vary else ())
+        extra = (BN_LIVE_PREFIXES if self.bn else (VARY_LIVE_PREFIXES if self.vary else
+                                                   (PLAIN_LIVE_PREFIXES if self.plain else ())))
         self.arena = ParamArena(list(module.named_parameters()), self.device, extra)
         self.ws = ops.GemmWorkspace(self.device)
         self._sel = {}                                  # constant 0/1 selection matrices of _wgrad_with_sums
@@ -392,6 +400,8 @@ class FusionEngine:
         self._er_pending = False
         self.shapes = {}
         self.train_mask = None            # cached train-mode selection (data independent)
+        # the plain fuser's exchange masks: all zero (the chain backward's exchange adjoint is then the identity)
+        self.plain_mask = torch.zeros(2, self.H, dtype=torch.float32, device=self.device) if self.plain else None
         self.drop_seed = 0x5EED
         self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -475,7 +485,7 @@ class FusionEngine:
             else:
                 ops.dropout_mask(w.drop_pool, DROP_P, self.drop_seed, self.drop_offset)
         tp = self.tp if (self.tp is not None and need_grad) else None
-        seam = self.use_fused_embed and mode == "train" and H <= 1024
+        seam = (self.use_fused_embed and mode == "train" and H <= 1024) or self.plain     # (plain: its only route)
         self._join_tail()
         if (self.overlap_planes and self.chain_bf3 and self.L == 1 and (self.use_fuser_chain or self.use_decoder_chain) and
                 self._chain_shape_ok(w)):
@@ -562,8 +572,9 @@ class FusionEngine:
             main.wait_event(fw["rgb_done"])
         if seam:
             # ---- one launch: slab sums of both projections, bias/ReLU, depth LayerNorm + ReLU (:183,195-197), token
-            # exchange + embd_drop (:56-62,83) and the fuser block's norm1 (transformerblock.py:122)
-            idx, mask = self._train_masks(B, S)
+            # exchange + embd_drop (:56-62,83) and the fuser block's norm1 (transformerblock.py:122); the plain fuser adds
+            # its modality token instead of the exchange (futr_safuser_depth.py:40-51)
+            idx, mask = (None, self.plain_mask) if self.plain else self._train_masks(B, S)
             dr = fw["dr"]
             if tp is not None:
                 dep_src, ns_d, bias_d = tp.summed(w), 1, a.p("depth_projection.bias")
@@ -574,11 +585,19 @@ class FusionEngine:
             ride = bool(self.ride_planes and self.chain_bf3 and not self._planes_forked and self.L == 1 and H < 512 and
                         not self._multi_stream() and not self.use_fused_decoder and self.use_paired_launches and
                         ((self.use_fuser_chain and self._chain_shape_ok(w)) or self._dec_chain_ok(w)))
-            ops.embed_fuse_fwd(fw["slabs_r"] if dr.splitk > 1 else w.rgb, dr.splitk if dr.splitk > 1 else 0,
-                               a.p("input_embed.bias"), dep_src, ns_d, bias_d, a.p("depth_layernorm.weight"),
-                               a.p("depth_layernorm.bias"), mask[0], mask[1], dm("x0"), dsc, a.p(pre + "norm1.weight"),
-                               a.p(pre + "norm1.bias"), w.rgb, w.dep_pre, w.mean_d, w.rstd_d, w.dep, w.x0, w.h1, w.m1, w.r1,
-                               planes=self.chain_planes() if ride else None)
+            rgb_src, ns_r = (fw["slabs_r"], dr.splitk) if dr.splitk > 1 else (w.rgb, 0)
+            planes = self.chain_planes() if ride else None
+            if self.plain:
+                ops.plain_fuse_fwd(rgb_src, ns_r, a.p("input_embed.bias"), dep_src, ns_d, bias_d,
+                                   a.p("depth_layernorm.weight"), a.p("depth_layernorm.bias"),
+                                   a.p("fuser.modality_token").view(-1), dm("x0"), dsc, a.p(pre + "norm1.weight"),
+                                   a.p(pre + "norm1.bias"), w.rgb, w.dep_pre, w.mean_d, w.rstd_d, w.dep, w.x0, w.h1, w.m1,
+                                   w.r1, planes=planes)
+            else:
+                ops.embed_fuse_fwd(rgb_src, ns_r, a.p("input_embed.bias"), dep_src, ns_d, bias_d,
+                                   a.p("depth_layernorm.weight"), a.p("depth_layernorm.bias"), mask[0], mask[1], dm("x0"),
+                                   dsc, a.p(pre + "norm1.weight"), a.p(pre + "norm1.bias"), w.rgb, w.dep_pre, w.mean_d,
+                                   w.rstd_d, w.dep, w.x0, w.h1, w.m1, w.r1, planes=planes)
             self._planes_rode = ride
         # ---- depth LayerNorm + ReLU first: it drains the deferred split-K slabs (:196-197)
         elif tp is not None:                      # the exchanged sum of the ranks' partial products, bias still to add
@@ -1261,6 +1280,8 @@ class FusionEngine:
              (w.glayers[self.L - 1]["caqin"], w.glayers[self.L - 1]["sain"], Q, a.g("query_embed.weight"))]
         if self.vary:                          # d alpha: the column sum of the exchange backward's per-element terms
             R.append((w.t_dal, None, 1, a.g("fuser.alpha").view(1, H)))
+        if self.plain:                         # d modality_token: the column sum of the seam's per-frame partials
+            R.append((w.t_tok, None, 1, a.g("fuser.modality_token").view(1, H)))
         w.rowsum_group = ops.RowsumGroup(R)
         # The LayerNorm partial sums are column sums as well: when a site's (weight, bias) gradients are adjacent in the
         # arena (they are: same size class, declaration order) its finalize is one more job of the row-sum launch.
@@ -1467,6 +1488,11 @@ class FusionEngine:
                 self._erank_join()
                 self._erank_backward(w, ws, dst=w.d_extra)
             w.tables[key].launch()
+            if self.plain:
+                # all-zero exchange masks: the chain's exchange adjoint is the identity and its input gradients stand; the
+                # modality token's per-frame partials from the chain's d_h1 / d_x1
+                ops.plain_fuse_bwd(w.d_h1, w.x0, w.m1, w.r1, a.p(pre + "norm1.weight"), w.d_x1, dmf("x0"), dsc, None, None,
+                                   None, None, None, None, None, None, None, None, w.t_tok)
             if self.vary:
                 # the chain's own exchange adjoint is the unscaled one: redo the seam from its d_h1 / d_x1 with alpha (its
                 # norm1 partials stand), then the depth LayerNorm + ReLU backward
@@ -1569,6 +1595,10 @@ class FusionEngine:
         mask = st["mask"]
         if chain:
             pass
+        elif self.plain:                   # norm1 backward + dropout + token partials + depth LayerNorm backward: one launch
+            ops.plain_fuse_bwd(w.d_h1, w.x0, w.m1, w.r1, a.p(pre + "norm1.weight"), w.d_x1, dmf("x0"), dsc, w.rgb, w.dep_pre,
+                               w.mean_d, w.rstd_d, a.p("depth_layernorm.weight"), a.p("depth_layernorm.bias"), w.d_rgb_pre,
+                               w.d_dep_pre, w.lnp_seam["n1"], w.lnp_seam["dep"], w.t_tok)
         elif st["seam"]:                    # norm1 backward + exchange backward + depth LayerNorm backward: one launch
             ops.embed_fuse_bwd(w.d_h1, w.x0, w.m1, w.r1, a.p(pre + "norm1.weight"), w.d_x1, w.d_x3, dmf("x0"), dsc, mask[0],
                                mask[1], w.rgb, w.dep_pre, w.mean_d, w.rstd_d, a.p("depth_layernorm.weight"),

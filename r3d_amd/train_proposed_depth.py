@@ -27,7 +27,8 @@ def _unwrap(model):
         m = m.module
     if not isinstance(m, (FUTR, FUTRDepthQuery)):
         raise TypeError("r3d_amd.train_proposed_depth drives r3d_amd.model.futr_safuser_tokenfusion.FUTR (or its "
-                        "BN-blend and activation-magnitude subclasses) and r3d_amd.model.futr_unsupervised_depth.FUTR")
+                        "BN-blend, activation-magnitude and plain SA-Fuser subclasses) and "
+                        "r3d_amd.model.futr_unsupervised_depth.FUTR")
     return m
 
 
