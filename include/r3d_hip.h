@@ -636,6 +636,8 @@ int r3d_erank_blocked_t(const float* x, int ld, int x_transposed, int R, int C, 
 int r3d_erank_bwd_coef(const float* sigma, const float* stats, const float* gout, float* coef, int C, int max_rank,
                        void* stream);
 int r3d_scale_rows(float* x, int ld, int rows, int cols, const float* coef, void* stream);
+/* y[r, :] = x[r, :] * coef[r] (y == x with the same ld: in place, r3d_scale_rows). */
+int r3d_scale_rows_into(const float* x, int ldx, float* y, int ldy, int rows, int cols, const float* coef, void* stream);
 /* The backward in its well-conditioned form: U = (X V) Sigma^-1, V^T = Sigma^-1 (2 I - U^T U) U^T X (one Neumann term of
  * (U^T U)^-1: the plain V^T = Sigma^-1 U^T X amplifies the residual coupling of a small column with a large one by
  * sigma_j / sigma_i), dX = U diag(g) V^T.  r3d_erank_bwd_coef2: cg[k] = gout * (d erank / d sigma_k) / sigma_k,
@@ -653,6 +655,12 @@ int64_t r3d_erank_lds_bytes_v(int R, int C);
 int r3d_erank_jacobi_warm(const float* x, int ld, int64_t batch_stride, int batch, int R, int C, int gram, float* sigma,
                           float* af_t, float* stats, int max_sweeps, const float* vt_in, float* vt_out, void* stream);
 int r3d_erank_vt_polish(const float* vt_raw, const float* gv, float* vt, int64_t n, void* stream);
+/* The kernel instance r3d_erank_jacobi_warm (blocked == 0; warm != 0: with vt_out) or r3d_erank_blocked_t (blocked != 0)
+ * launches for an [R, C] matrix; host only, no launch.  out[9] = {blocked, G, NCH, EXACT, level, warm, b, nreal, nblk}:
+ * level = the LDS kernel's pair order (0 general, 1 level order, 2 level order in 2 x 2 blocks); b, nreal, nblk = the
+ * blocked route's columns per block, blocks of real columns and blocks swept (even: a dummy block when nreal is odd).
+ * R3D_EINVAL when the route does not take the matrix.  The launchers dispatch on the same plan. */
+int r3d_erank_plan(int R, int C, int warm, int blocked, int32_t* out);
 
 /* ---- depth-as-query model (reference model/futr_unsupervised_depth.py) ------------------------------------------------
  * r3d_posenc_fwd / bwd: PositionalEncoding.forward (model/extras/position.py:29-35) on b-major rows,

@@ -259,6 +259,7 @@ _SIGNATURES = {
     "r3d_erank_bwd_coef2": ([_P, _P, _P, _P, _P, _I, _I, _P], C.c_int),
     "r3d_erank_bwd_fix": ([_P, _P, _P, _I, _I, _P], C.c_int),
     "r3d_scale_rows": ([_P, _I, _I, _I, _P, _P], C.c_int),
+    "r3d_scale_rows_into": ([_P, _I, _P, _I, _I, _I, _P, _P], C.c_int),
     "r3d_posenc_fwd": ([_P, _I, _P, _I, _I, _P, _F, _P, _I, _I, _I, _P], C.c_int),
     "r3d_posenc_bwd": ([_P, _I, _P, _F, _P, _I, _P, _I, _I, _I, _P], C.c_int),
     "r3d_avgpool_rows_fwd": ([_P, _I, _P, _I, _I, _I, _I, _I, _P], C.c_int),
@@ -268,6 +269,7 @@ _SIGNATURES = {
     "r3d_erank_lds_bytes_v": ([_I, _I], C.c_int64),
     "r3d_erank_jacobi_warm": ([_P, _I, _L, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P], C.c_int),
     "r3d_erank_vt_polish": ([_P, _P, _P, _L, _P], C.c_int),
+    "r3d_erank_plan": ([_I, _I, _I, _I, _P], C.c_int),
     "r3d_clip_collate": ([C.POINTER(ClipCollateJob), _P], C.c_int),
 }
 

@@ -653,11 +653,13 @@ __global__ __launch_bounds__(256) void erank_bwd_fix_kernel(float* w, const floa
         w[e] = cg[e / cols] * (2.f * w[e] - p[e]);
 }
 
-__global__ __launch_bounds__(256) void scale_rows_kernel(float* x, int ld, int rows, int cols, const float* coef) {
+// y[r, c] = x[r, c] * coef[r]  (y == x: in place)
+__global__ __launch_bounds__(256) void scale_rows_kernel(const float* x, int ldx, float* y, int ldy, int rows, int cols,
+                                                         const float* coef) {
     const size_t total = (size_t)rows * cols;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const int r = (int)(e / cols), c = (int)(e % cols);
-        x[(size_t)r * ld + c] *= coef[r];
+        y[(size_t)r * ldy + c] = x[(size_t)r * ldx + c] * coef[r];
     }
 }
 
@@ -684,20 +686,60 @@ R3D_EXPORT int64_t r3d_erank_lds_bytes_v(int R, int C) {
     return ((int64_t)((C + 1) & ~1) * (erank_rp(R) + ((C + 3) & ~3)) + ((C + 1) & ~1)) * 4;
 }
 
-template <int G, int NCH, bool EXACT>
+template <int G, int NCH, bool EXACT, int HALVE = 0>
 static int erank_launch2(const ErankArgs& a, int batch, int64_t lds, hipStream_t st) {
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)erank_jacobi_kernel<G, NCH, EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)erank_jacobi_kernel<G, NCH, EXACT, HALVE>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL((erank_jacobi_kernel<G, NCH, EXACT>), dim3(batch), dim3(kJacThreads), (size_t)lds, st, a);
+    hipLaunchKernelGGL((erank_jacobi_kernel<G, NCH, EXACT, HALVE>), dim3(batch), dim3(kJacThreads), (size_t)lds, st, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }
+
+#ifndef R3D_JAC_HALVING
+#define R3D_JAC_HALVING 1
+#endif
+#ifndef R3D_JAC_LANES
+#define R3D_JAC_LANES 8
+#endif
+#ifndef R3D_JAC_BLOCK2
+#define R3D_JAC_BLOCK2 0        // measured (round 3): 90 us per sweep and 8 sweeps against 81 us and 7 for MODE 1 at [128, 128]:
+#endif                          // half the LDS traffic and barriers, but each super-round is TWO dependent rotation stages and
+                                // the round was a latency chain already (dot -> reduce -> rcp / sqrt / rsq -> rotate), not
+                                // LDS- or barrier-bound; kept under the macro, tests pass in both modes
+
+/* The instance r3d_erank_jacobi_warm launches for an [R, C] matrix (warm: the basis rides along): level = HALVE of
+ * erank_jacobi_kernel (0 the general order), lane group G, NCH chunks per lane (0: any length), EXACT layout.  The launcher
+ * dispatches on this plan and r3d_erank_plan reports it, so the two cannot disagree. */
+struct ErankLdsPlan { int level, G, nch, exact; };
+static ErankLdsPlan erank_lds_plan(int R, int C, bool warm) {
+    const int npairs = ((C + 1) & ~1) / 2;
+    const int rp4 = erank_rp(R) / 4;
+    const int s4 = rp4 + (warm ? ((C + 3) & ~3) / 4 : 0);           // 16-byte chunks per column
+    if (R3D_JAC_HALVING && !warm && C >= 32 && C <= 128 && (C & (C - 1)) == 0 && (R & 63) == 0 && R <= 512) {
+        // power-of-two column count, whole chunks: the level order with the first column of every pair in registers
+        const int r64 = R / 64;
+        if (R3D_JAC_BLOCK2 && C >= 8 && (r64 == 1 || r64 == 2 || r64 == 4))
+            return {2, 16, r64, 1};                                  // the level order in 2 x 2 register blocks
+        if (R3D_JAC_LANES == 8 && (r64 == 1 || r64 == 2 || r64 == 4)) return {1, 8, 2 * r64, 1};
+        if (r64 == 1 || r64 == 2 || r64 == 4 || r64 == 8) return {1, 16, r64, 1};
+    }
+    int G, nch;
+    if (npairs > 16) {                          // 16 lanes per pair: 64 pairs per pass
+        G = 16;
+        nch = s4 <= 16 ? 1 : s4 <= 32 ? 2 : s4 <= 64 ? 4 : s4 <= 128 ? 8 : 0;
+    } else {
+        G = 64;
+        nch = s4 <= 64 ? 1 : s4 <= 128 ? 2 : s4 <= 256 ? 4 : s4 <= 512 ? 8 : 0;
+    }
+    return {0, G, nch, (nch > 0 && s4 == G * nch && rp4 % G == 0) ? 1 : 0};
+}
+
 template <int G, int NCH>
-static int erank_launch(const ErankArgs& a, int batch, int64_t lds, hipStream_t st) {
-    const int rp4 = erank_rp(a.R) / 4, s4 = rp4 + (a.vt_out ? ((a.C + 3) & ~3) / 4 : 0);
-    if (NCH > 0 && s4 == G * NCH && rp4 % G == 0) return erank_launch2<G, NCH, true>(a, batch, lds, st);
+static int erank_launch_general(const ErankLdsPlan& p, const ErankArgs& a, int batch, int64_t lds, hipStream_t st) {
+    if (p.exact) return erank_launch2<G, NCH, true>(a, batch, lds, st);
     return erank_launch2<G, NCH, false>(a, batch, lds, st);
 }
 
@@ -728,66 +770,48 @@ R3D_EXPORT int r3d_erank_jacobi_warm(const float* x, int ld, int64_t batch_strid
     if (af_t && (R & 3) == 0) R3D_REQUIRE(r3d_aligned16(af_t));
     ErankArgs a{x, ld, (long long)batch_stride, R, C, sigma, af_t, stats, gram, max_sweeps > 0 ? max_sweeps : 30, vt_in, vt_out};
     hipStream_t st = (hipStream_t)stream;
-    const int npairs = ((C + 1) & ~1) / 2;
-    const int s4 = erank_rp(R) / 4 + (vt_out ? ((C + 3) & ~3) / 4 : 0);       // 16-byte chunks per column
-#ifndef R3D_JAC_HALVING
-#define R3D_JAC_HALVING 1
-#endif
-    if (R3D_JAC_HALVING && !vt_out && C >= 32 && C <= 128 && (C & (C - 1)) == 0 && (R & 63) == 0 && R <= 512) {
-        // power-of-two column count, whole chunks: the level order with the first column of every pair in registers
-        auto go = [&](auto kern) {
-            if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return (int)e;
-            }
-            hipLaunchKernelGGL(kern, dim3(batch), dim3(kJacThreads), (size_t)lds, st, a);
-            R3D_LAUNCH_CHECK();
-            return (int)R3D_OK;
-        };
-#ifndef R3D_JAC_LANES
-#define R3D_JAC_LANES 8
-#endif
-#ifndef R3D_JAC_BLOCK2
-#define R3D_JAC_BLOCK2 0        // measured (round 3): 90 us per sweep and 8 sweeps against 81 us and 7 for MODE 1 at [128, 128]:
-#endif                          // half the LDS traffic and barriers, but each super-round is TWO dependent rotation stages and
-                                // the round was a latency chain already (dot -> reduce -> rcp / sqrt / rsq -> rotate), not
-                                // LDS- or barrier-bound; kept under the macro, tests pass in both modes
-        if (R3D_JAC_BLOCK2 && C >= 8) {                // the level order in 2 x 2 register blocks (16 lanes per group)
-            switch (R / 64) {
-                case 1: return go(erank_jacobi_kernel<16, 1, true, 2>);
-                case 2: return go(erank_jacobi_kernel<16, 2, true, 2>);
-                case 4: return go(erank_jacobi_kernel<16, 4, true, 2>);
-                default: break;
-            }
-        }
-        if (R3D_JAC_LANES == 8) {
-            switch (R / 64) {
-                case 1: return go(erank_jacobi_kernel<8, 2, true, 1>);
-                case 2: return go(erank_jacobi_kernel<8, 4, true, 1>);
-                case 4: return go(erank_jacobi_kernel<8, 8, true, 1>);
-                default: break;
-            }
-        }
-        switch (R / 64) {
-            case 1: return go(erank_jacobi_kernel<16, 1, true, 1>);
-            case 2: return go(erank_jacobi_kernel<16, 2, true, 1>);
-            case 4: return go(erank_jacobi_kernel<16, 4, true, 1>);
-            case 8: return go(erank_jacobi_kernel<16, 8, true, 1>);
-            default: break;
+    const ErankLdsPlan p = erank_lds_plan(R, C, vt_out != nullptr);
+    if (p.level == 2) {                             // (R3D_JAC_BLOCK2)
+        switch (p.nch) {
+            case 1: return erank_launch2<16, 1, true, 2>(a, batch, lds, st);
+            case 2: return erank_launch2<16, 2, true, 2>(a, batch, lds, st);
+            case 4: return erank_launch2<16, 4, true, 2>(a, batch, lds, st);
+            default: return R3D_EINVAL;
         }
     }
-    if (npairs > 16) {                          // 16 lanes per pair: 64 pairs per pass
-        if (s4 <= 16) return erank_launch<16, 1>(a, batch, lds, st);
-        if (s4 <= 32) return erank_launch<16, 2>(a, batch, lds, st);
-        if (s4 <= 64) return erank_launch<16, 4>(a, batch, lds, st);
-        if (s4 <= 128) return erank_launch<16, 8>(a, batch, lds, st);
-        return erank_launch<16, 0>(a, batch, lds, st);
+    if (p.level == 1 && p.G == 8) {
+        switch (p.nch) {
+            case 2: return erank_launch2<8, 2, true, 1>(a, batch, lds, st);
+            case 4: return erank_launch2<8, 4, true, 1>(a, batch, lds, st);
+            case 8: return erank_launch2<8, 8, true, 1>(a, batch, lds, st);
+            default: return R3D_EINVAL;
+        }
     }
-    if (s4 <= 64) return erank_launch<64, 1>(a, batch, lds, st);
-    if (s4 <= 128) return erank_launch<64, 2>(a, batch, lds, st);
-    if (s4 <= 256) return erank_launch<64, 4>(a, batch, lds, st);
-    if (s4 <= 512) return erank_launch<64, 8>(a, batch, lds, st);
-    return erank_launch<64, 0>(a, batch, lds, st);
+    if (p.level == 1) {
+        switch (p.nch) {
+            case 1: return erank_launch2<16, 1, true, 1>(a, batch, lds, st);
+            case 2: return erank_launch2<16, 2, true, 1>(a, batch, lds, st);
+            case 4: return erank_launch2<16, 4, true, 1>(a, batch, lds, st);
+            case 8: return erank_launch2<16, 8, true, 1>(a, batch, lds, st);
+            default: return R3D_EINVAL;
+        }
+    }
+    if (p.G == 16) {
+        switch (p.nch) {
+            case 1: return erank_launch_general<16, 1>(p, a, batch, lds, st);
+            case 2: return erank_launch_general<16, 2>(p, a, batch, lds, st);
+            case 4: return erank_launch_general<16, 4>(p, a, batch, lds, st);
+            case 8: return erank_launch_general<16, 8>(p, a, batch, lds, st);
+            default: return erank_launch_general<16, 0>(p, a, batch, lds, st);
+        }
+    }
+    switch (p.nch) {
+        case 1: return erank_launch_general<64, 1>(p, a, batch, lds, st);
+        case 2: return erank_launch_general<64, 2>(p, a, batch, lds, st);
+        case 4: return erank_launch_general<64, 4>(p, a, batch, lds, st);
+        case 8: return erank_launch_general<64, 8>(p, a, batch, lds, st);
+        default: return erank_launch_general<64, 0>(p, a, batch, lds, st);
+    }
 }
 
 /* Block size (columns per block) of the two-level Jacobi for column length R: two blocks must fit one CU's LDS. */
@@ -831,10 +855,26 @@ static int erank_blk_sweeps2(const ErankBlk& g, int ms, int64_t lds, hipStream_t
     return R3D_OK;
 }
 
+/* The instance r3d_erank_blocked_t launches for an [R, C] matrix: b columns per block (two blocks fit the LDS), NCH
+ * chunks per lane of erank_blk_round_kernel (0: any length), EXACT layout, nreal blocks of real columns, nblk (even; a
+ * dummy block when nreal is odd).  The launcher dispatches on this plan and r3d_erank_plan reports it.  Returns false
+ * when even two 2-column blocks exceed the LDS. */
+struct ErankBlkPlan { int b, nch, exact, nreal, nblk; int64_t lds; };
+static bool erank_blk_plan(int R, int C, ErankBlkPlan& p) {
+    p.b = erank_blk_b(R);
+    const int Rp = erank_rp(R), rp4 = Rp / 4;
+    p.lds = ((int64_t)2 * p.b * Rp + 2 * p.b) * 4;
+    p.nch = rp4 <= 64 ? 1 : rp4 <= 128 ? 2 : rp4 <= 256 ? 4 : rp4 <= 512 ? 8 : 0;
+    p.exact = (p.nch > 0 && rp4 == 64 * p.nch) ? 1 : 0;
+    p.nreal = r3d_cdiv(C, p.b);
+    p.nblk = (p.nreal + 1) & ~1;
+    return p.lds <= 150 * 1024;
+}
+
 template <int NCH>
-static int erank_blk_sweeps(const ErankBlk& g, int ms, int64_t lds, hipStream_t st) {
-    if (NCH > 0 && (g.Rp >> 2) == 64 * NCH) return erank_blk_sweeps2<NCH, true>(g, ms, lds, st);
-    return erank_blk_sweeps2<NCH, false>(g, ms, lds, st);
+static int erank_blk_sweeps(const ErankBlkPlan& p, const ErankBlk& g, int ms, hipStream_t st) {
+    if (p.exact) return erank_blk_sweeps2<NCH, true>(g, ms, p.lds, st);
+    return erank_blk_sweeps2<NCH, false>(g, ms, p.lds, st);
 }
 
 /* Effective rank of ONE matrix X[R, C] (row-major, leading dimension ld) of any size: two-level one-sided Jacobi
@@ -856,29 +896,47 @@ R3D_EXPORT int r3d_erank_blocked_t(const float* x, int ld, int x_transposed, int
                                    int* ctrl, float* stats, int max_sweeps, void* stream) {
     R3D_REQUIRE(x && sigma && af_t && ctrl && stats && R > 0 && C > 0 && ld >= (x_transposed ? R : C));
     R3D_REQUIRE(r3d_aligned16(af_t));
-    const int b = erank_blk_b(R);
+    ErankBlkPlan p;
+    R3D_REQUIRE(erank_blk_plan(R, C, p));
     const int Rp = erank_rp(R);
-    const int64_t lds = ((int64_t)2 * b * Rp + 2 * b) * 4;
-    R3D_REQUIRE(lds <= 150 * 1024);
     const int ms = max_sweeps > 0 ? max_sweeps : 16;
-    const int nreal = r3d_cdiv(C, b);
-    const int nblk = (nreal + 1) & ~1;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(ctrl, 0, sizeof(int) * (4 + ms), st);
     if (e != hipSuccess) return (int)e;
-    ErankBlk g{af_t, R, Rp, C, b, nblk, nreal, ctrl};
-    hipLaunchKernelGGL(erank_blk_init_kernel, dim3(r3d_cdiv(nreal * b, 32), r3d_cdiv(Rp, 32)), dim3(256), 0, st, x, ld, g, x_transposed ? 1 : 0);
-    const int rp4 = Rp / 4;
+    ErankBlk g{af_t, R, Rp, C, p.b, p.nblk, p.nreal, ctrl};
+    hipLaunchKernelGGL(erank_blk_init_kernel, dim3(r3d_cdiv(p.nreal * p.b, 32), r3d_cdiv(Rp, 32)), dim3(256), 0, st, x, ld, g,
+                       x_transposed ? 1 : 0);
     int rc;
-    if (rp4 <= 64) rc = erank_blk_sweeps<1>(g, ms, lds, st);
-    else if (rp4 <= 128) rc = erank_blk_sweeps<2>(g, ms, lds, st);
-    else if (rp4 <= 256) rc = erank_blk_sweeps<4>(g, ms, lds, st);
-    else if (rp4 <= 512) rc = erank_blk_sweeps<8>(g, ms, lds, st);
-    else rc = erank_blk_sweeps<0>(g, ms, lds, st);
+    switch (p.nch) {
+        case 1: rc = erank_blk_sweeps<1>(p, g, ms, st); break;
+        case 2: rc = erank_blk_sweeps<2>(p, g, ms, st); break;
+        case 4: rc = erank_blk_sweeps<4>(p, g, ms, st); break;
+        case 8: rc = erank_blk_sweeps<8>(p, g, ms, st); break;
+        default: rc = erank_blk_sweeps<0>(p, g, ms, st); break;
+    }
     if (rc != R3D_OK) return rc;
     hipLaunchKernelGGL(erank_blk_sigma_kernel, dim3(r3d_cdiv(C, kJacThreads / 64)), dim3(kJacThreads), 0, st, g, sigma);
     hipLaunchKernelGGL(erank_blk_stats_kernel, dim3(1), dim3(kJacThreads), 0, st, g, (const float*)sigma, stats);
     R3D_LAUNCH_CHECK();
+    return R3D_OK;
+}
+
+/* The kernel instance r3d_erank_jacobi_warm (blocked == 0; warm != 0: with vt_out) or r3d_erank_blocked_t (blocked != 0)
+ * launches for an [R, C] matrix, host only.  out[9] = {blocked, G, NCH, EXACT, level, warm, b, nreal, nblk}: level is the
+ * LDS kernel's pair order (0 general, 1 level order, 2 level order in 2 x 2 blocks); b, nreal, nblk are the blocked
+ * route's block size and block counts (0 for the LDS kernel).  R3D_EINVAL when the route does not take the matrix. */
+R3D_EXPORT int r3d_erank_plan(int R, int C, int warm, int blocked, int32_t* out) {
+    R3D_REQUIRE(out && R > 0 && C > 0);
+    for (int i = 0; i < 9; ++i) out[i] = 0;
+    if (blocked) {
+        ErankBlkPlan p;
+        R3D_REQUIRE(erank_blk_plan(R, C, p));
+        out[0] = 1; out[1] = 64; out[2] = p.nch; out[3] = p.exact; out[6] = p.b; out[7] = p.nreal; out[8] = p.nblk;
+        return R3D_OK;
+    }
+    R3D_REQUIRE((warm ? r3d_erank_lds_bytes_v(R, C) : r3d_erank_lds_bytes(R, C)) <= 160 * 1024 - 256);
+    const ErankLdsPlan p = erank_lds_plan(R, C, warm != 0);
+    out[1] = p.G; out[2] = p.nch; out[3] = p.exact; out[4] = p.level; out[5] = warm ? 1 : 0;
     return R3D_OK;
 }
 
@@ -897,7 +955,7 @@ R3D_EXPORT int r3d_erank_bwd_coef(const float* sigma, const float* stats, const 
  * small sigma_i, the residual coupling e_ij of column i with every large column j amplified by sigma_j / sigma_i (the
  * two-GEMM form Af diag(g / sigma^3) Af^T X has exactly that error: 0.4 of the gradient's scale with LAPACK's fp32
  * vectors at the BASELINE shapes).  One Neumann term of (U^T U)^-1 removes it:  V^T = Sigma^-1 (2 I - U^T U) U^T X up to
- * e^2 sigma_j / sigma_i.  The host composes: scale_rows(af_t, inv) -> W = U^T X -> G = U^T U -> P = G W ->
+ * e^2 sigma_j / sigma_i.  The host composes: scale_rows_into(af_t, inv, ut) -> W = U^T X -> G = U^T U -> P = G W ->
  * r3d_erank_bwd_fix: W <- diag(cg) (2 W - P) -> dX = U W.  r3d_erank_bwd_coef2 fills cg[k] = gout * (d erank / d sigma_k)
  * / sigma_k and inv[k] = 1 / sigma_k (both zero where r3d_erank_bwd_coef's coefficient is). */
 R3D_EXPORT int r3d_erank_bwd_coef2(const float* sigma, const float* stats, const float* gout, float* cg, float* inv, int C,
@@ -919,12 +977,21 @@ R3D_EXPORT int r3d_erank_bwd_fix(float* w, const float* p, const float* cg, int 
     return R3D_OK;
 }
 
+R3D_EXPORT int r3d_scale_rows_into(const float* x, int ldx, float* y, int ldy, int rows, int cols, const float* coef,
+                                   void* stream);
 /* x[r, :] *= coef[r] */
 R3D_EXPORT int r3d_scale_rows(float* x, int ld, int rows, int cols, const float* coef, void* stream) {
-    R3D_REQUIRE(x && coef && rows > 0 && cols > 0 && ld >= cols);
+    return r3d_scale_rows_into(x, ld, x, ld, rows, cols, coef, stream);
+}
+
+/* y[r, :] = x[r, :] * coef[r]; y == x (same ld) works in place, otherwise the two must not overlap. */
+R3D_EXPORT int r3d_scale_rows_into(const float* x, int ldx, float* y, int ldy, int rows, int cols, const float* coef,
+                                   void* stream) {
+    R3D_REQUIRE(x && y && coef && rows > 0 && cols > 0 && ldx >= cols && ldy >= cols);
+    R3D_REQUIRE(x != y || ldx == ldy);
     const size_t total = (size_t)rows * cols;
     const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ld, rows, cols, coef);
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, rows, cols, coef);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }

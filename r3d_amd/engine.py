@@ -780,7 +780,8 @@ class FusionEngine:
         when the sweep ran on fused^T (wide token matrices) the same products in the transposed orientation."""
         from .erank import ErankBackward
         if not hasattr(w, "er_bwd"):
-            w.er_bwd = ErankBackward(w.N, self.H, w.er_blk is not None and w.er_flip, self.device)
+            w.er_bwd = ErankBackward(w.N, self.H, w.er_blk is not None and w.er_flip, self.device,
+                                     ld=w.er_blk.Rp if w.er_blk is not None else None)
         w.er_gout.fill_(-float(self.erank_weight))
         A = w.er_blk.af_t if w.er_blk is not None else w.er_af[0]
         w.er_bwd.run(w.fused, A, w.er_sigma[0], w.er_stats[0], w.er_gout, dst if dst is not None else w.d_fused2,

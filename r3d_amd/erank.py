@@ -24,30 +24,36 @@ class ErankBackward:
     first order (measured against fp64 autograd through svdvals: 6-8x closer at sigma_max / sigma_min = 1e4; what remains
     is the fp32 rounding of the rotated columns themselves, ~eps * sigma_max / sigma_i in direction i).  Four GEMMs, three
     row-wise kernels, all enqueued on the current stream; buffers are allocated once (the training step replays it in a
-    hipGraph).  flip: the sweep ran on X^T (A is [R, C] for X [R, C]); the same products in the transposed orientation."""
+    hipGraph).  flip: the sweep ran on X^T (A is [R, C] for X [R, C]); the same products in the transposed orientation.
+    A itself is only read: U^T goes to a buffer of this object's (row stride ld, A's), so a second backward over the same
+    sweep -- retain_graph, or the step's backward followed by another -- sees the same A and gives the same gradient."""
 
-    def __init__(self, R, C, flip, device):
+    def __init__(self, R, C, flip, device, ld=None):
         self.flip, self.R, self.C = bool(flip), R, C
         k = R if flip else C                       # singular values / rows of A
+        n = C if flip else R                       # length of A's rows
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)     # noqa: E731
         self.cg, self.inv, self.w, self.g, self.p = f(k), f(k), f(k, k), f(k, k), f(k, k)
+        self.ut = f(k, n if ld is None else ld)[:, :n]
 
     def run(self, x, a_rows, sigma, stats, gout, out, accumulate, ws):
-        """x [R, C]; a_rows [k, len] view (row stride may exceed len), scaled IN PLACE to U^T; out [R, C]."""
+        """x [R, C]; a_rows [k, len] view (row stride may exceed len; not written); out [R, C]."""
         k = self.R if self.flip else self.C
         ops.erank_bwd_coef2(sigma, stats, gout, self.cg, self.inv, max_rank=min(self.R, self.C))
-        ops.scale_rows(a_rows, self.inv)                                   # A -> U^T
+        ut = self.ut
+        assert ut.shape == a_rows.shape and ut.stride(0) == a_rows.stride(0), (ut.shape, ut.stride(), a_rows.stride())
+        ops.scale_rows_into(a_rows, self.inv, ut)                          # U^T = diag(1 / sigma) A
         if self.flip:
-            ops.gemm(GEMM_NT, a_rows, x, self.w, ws=ws)                    # U^T X^T            [R, R]
+            ops.gemm(GEMM_NT, ut, x, self.w, ws=ws)                        # U^T X^T            [R, R]
         else:
-            ops.gemm(GEMM_NN, a_rows, x, self.w, ws=ws)                    # U^T X              [C, C]
-        ops.gemm(GEMM_NT, a_rows, a_rows, self.g, ws=ws)                   # U^T U
+            ops.gemm(GEMM_NN, ut, x, self.w, ws=ws)                        # U^T X              [C, C]
+        ops.gemm(GEMM_NT, ut, ut, self.g, ws=ws)                           # U^T U
         ops.gemm(GEMM_NN, self.g, self.w, self.p, ws=ws)
         ops.erank_bwd_fix(self.w, self.p, self.cg)                         # diag(g / sigma) (2 W - (U^T U) W)
         if self.flip:
-            ops.gemm(GEMM_TN, self.w, a_rows, out, accumulate=accumulate, ws=ws)       # (U W)^T = W^T U^T
+            ops.gemm(GEMM_TN, self.w, ut, out, accumulate=accumulate, ws=ws)           # (U W)^T = W^T U^T
         else:
-            ops.gemm(GEMM_TN, a_rows, self.w, out, accumulate=accumulate, ws=ws)       # U W
+            ops.gemm(GEMM_TN, ut, self.w, out, accumulate=accumulate, ws=ws)           # U W
         assert k == self.w.shape[0]
 
 
@@ -90,8 +96,8 @@ class _ERankBlocked(torch.autograd.Function):
         xx, sigma, stats, af_t = ctx.saved_tensors
         R, C = xx.shape
         dx = torch.empty_like(xx)
-        ErankBackward(R, C, False, xx.device).run(xx, af_t[:C], sigma, stats, gout.contiguous().reshape(1).float(), dx, False,
-                                                  ops.GemmWorkspace(xx.device))
+        ErankBackward(R, C, False, xx.device, ld=af_t.stride(0)).run(xx, af_t[:C], sigma, stats, gout.contiguous().reshape(1).float(),
+                                                                     dx, False, ops.GemmWorkspace(xx.device))
         return dx.t().contiguous() if ctx.flip else dx
 
 

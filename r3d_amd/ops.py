@@ -978,6 +978,21 @@ def erank_blocked_supported(R, Cc):
     return _lib.load().r3d_erank_blocked_sizes(R, Cc, 16, ctypes.cast(sz, ctypes.c_void_p)) == 0
 
 
+ERANK_PLAN_FIELDS = ("blocked", "G", "nch", "exact", "level", "warm", "b", "nreal", "nblk")
+
+
+def erank_plan(R, Cc, warm=False, blocked=False):
+    """The kernel instance the Jacobi launcher takes for an [R, C] matrix (host only, no launch; r3d_erank_plan): a dict of
+    ERANK_PLAN_FIELDS -- the LDS kernel (blocked=False; warm: erank_jacobi_warm's basis rides along) reports its pair order
+    `level`, lane group G, NCH and EXACT; the blocked one (r3d_erank_blocked_t) its block size b, NCH, EXACT, nreal, nblk.
+    None when the route does not take the matrix."""
+    out = (C.c_int32 * 9)()
+    rc = _lib.load().r3d_erank_plan(R, Cc, 1 if warm else 0, 1 if blocked else 0, C.cast(out, C.c_void_p))
+    if rc != 0:
+        return None
+    return dict(zip(ERANK_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def erank_jacobi(x, sigma, stats, *, af_t=None, gram=False, max_sweeps=30):
     """x: [batch, R, C] contiguous (or [R, C])."""
     lib = _lib.load()
@@ -1066,6 +1081,13 @@ def scale_rows(x, coef):
     lib = _lib.load()
     rows, cols = x.shape
     check(lib.r3d_scale_rows(_p(x), _ld(x), rows, cols, _p(coef), _stream()), "r3d_scale_rows")
+
+
+def scale_rows_into(x, coef, y):
+    """y = diag(coef) x (x, y: [rows, cols] row-major views, any row strides; y must not overlap x)."""
+    rows, cols = x.shape
+    assert tuple(y.shape) == (rows, cols) and x.stride(1) == 1 and y.stride(1) == 1
+    check(_lib.load().r3d_scale_rows_into(_p(x), _ld(x), _p(y), _ld(y), rows, cols, _p(coef), _stream()), "r3d_scale_rows_into")
 
 
 def erank_fits_warm(R, Cc):

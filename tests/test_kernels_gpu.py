@@ -676,7 +676,9 @@ def test_gemm_bf16x3_uniform_wave_tile(ops, M, N, K, splits):
 # effective rank
 # ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("R,Cc", [(128, 128), (40, 24), (256, 128), (33, 64), (64, 512), (1024, 32), (16, 16), (127, 129),
-                                  (64, 64), (64, 32), (128, 32), (512, 64), (192, 128)])   # level order: 8 / 16 lanes, C = 32..128
+                                  (64, 64), (64, 32), (128, 32), (512, 64), (192, 128)])
+# (level order, 8 / 16 lanes: (128, 128), (256, 128), (64, 64), (64, 32), (128, 32), (512, 64); (192, 128) has R / 64 = 3,
+#  for which there is no level-order instance: the general kernel, G 16 NCH 4 -- ops.erank_plan reports each)
 def test_erank_jacobi_vs_svdvals(ops, R, Cc):
     from oracle import futr_oracle as O
     x = rnd(R, Cc, seed=R) @ torch.diag(torch.linspace(0.05, 2.0, Cc)) + 0.3
