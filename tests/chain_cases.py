@@ -57,10 +57,10 @@ def case_id(c):
     return f"B{c.B}-S{c.S}-K{c.K}-{p}"
 
 
-def make_batch(c, seed=BATCH_SEED):
+def make_batch(c, seed=BATCH_SEED, depth_hw=(224, 224)):
     """[features, depth, past_label, trans_dur_future, trans_future_target] (torch, CPU) for a case row."""
     pad_idx = c.K + 1
-    b = synth.make_batch(c.B, c.S, c.K, pad_idx, seed, pad_tail=(c.pad == "tail"))
+    b = synth.make_batch(c.B, c.S, c.K, pad_idx, seed, pad_tail=(c.pad == "tail"), depth_hw=depth_hw)
     if not isinstance(c.pad, str):
         assert len(c.pad) == c.B and all(1 <= n <= c.S for n in c.pad)
         feats, depth, lab = b[0], b[1], b[2]

@@ -422,6 +422,57 @@ def test_colabssum_and_select_from_sums(ops, oracle_lib):
         assert np.array_equal(idx[v].cpu().numpy(), want)
 
 
+SELECT_C = [40, 136, 200, 520, 1000, 1032, 2048]      # off the 64-column grid, past 1024 and the engine's widest row
+
+
+@pytest.mark.parametrize("Cc", SELECT_C)
+def test_token_select_off_grid_and_wide(ops, oracle_lib, Cc):
+    """All-equal scores (the tie path), distinct scores, and few-valued scores (ties across the k-th boundary), bit for bit
+    against the oracle's torch.topk rule; the used_serial flags name the path each vector took."""
+    from oracle import futr_oracle as O
+    rng = np.random.default_rng(Cc)
+    k = Cc // 4
+    vecs = [np.full(Cc, 1.0 / (2 * 16 * Cc), np.float32), rng.permutation(Cc).astype(np.float32) / Cc,
+            rng.random(Cc).astype(np.float32), rng.integers(0, 3, Cc).astype(np.float32),
+            rng.integers(0, 7, Cc).astype(np.float32)]
+    s = torch.from_numpy(np.stack(vecs))
+    idx = torch.full((len(vecs), k), -1, dtype=torch.int64, device="cuda")
+    mask = torch.full((len(vecs), Cc), -1.0, device="cuda")
+    used = torch.full((len(vecs),), -1, dtype=torch.int32, device="cuda")
+    ops.token_select(k, idx, mask, score_f=dev(s), used_serial=used)
+    torch.cuda.synchronize()
+    for v in range(len(vecs)):
+        want = O.select_smallest(vecs[v], k)
+        assert np.array_equal(idx[v].cpu().numpy(), want), (Cc, v)
+        m = np.zeros(Cc, np.float32)
+        m[want] = 1
+        assert np.array_equal(mask[v].cpu().numpy(), m), (Cc, v)
+    assert used.cpu().tolist()[:3] == [1, 0, 0], (Cc, used.cpu().tolist())     # all-equal: tie path; distinct: parallel
+
+
+@pytest.mark.parametrize("Cc", SELECT_C)
+def test_colabssum_and_select_from_sums_off_grid(ops, oracle_lib, Cc):
+    """The validation route: |x| column sums over a row count off the 64-row grid, divided by it, then selected."""
+    from oracle import futr_oracle as O
+    rows = 150
+    x = rnd(2, rows, Cc, seed=Cc)
+    sums = torch.full((2, Cc), float("nan"), dtype=torch.float64, device="cuda")
+    ops.colabssum(dev(x[0]), sums[0])
+    ops.colabssum(dev(x[1]), sums[1])
+    idx = torch.empty(2, Cc // 4, dtype=torch.int64, device="cuda")
+    mask = torch.empty(2, Cc, device="cuda")
+    ops.token_select(Cc // 4, idx, mask, score_sum=sums, count=float(rows))
+    torch.cuda.synchronize()
+    assert_close(sums.cpu(), x.double().abs().sum(1), 1e-12, 1e-9, f"abs sums C{Cc}")
+    for v in range(2):
+        want = O.select_smallest((x[v].double().abs().sum(0) / rows).float().numpy(), Cc // 4)   # the kernel's scores
+        assert np.array_equal(want, O.select_smallest(x[v].abs().mean(0).numpy(), Cc // 4)), (Cc, v, "reseed: fp32 tie")
+        assert np.array_equal(idx[v].cpu().numpy(), want), (Cc, v)
+        m = np.zeros(Cc, np.float32)
+        m[want] = 1
+        assert np.array_equal(mask[v].cpu().numpy(), m), (Cc, v)
+
+
 def test_token_exchange_fwd_bwd(ops):
     N, H = 37, 64
     rgb, dep = rnd(N, H, seed=1).relu(), rnd(N, H, seed=2).relu()

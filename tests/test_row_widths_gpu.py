@@ -137,6 +137,100 @@ def test_embed_fuse_fwd_bwd(ops, H, ns_r, ns_d, drop, misalign):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# plain SA-Fuser seam (plainfuse.hip): the embedding seam with the modality token added instead of the exchange
+# ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,ns_r,ns_d,drop,misalign", EMBED_CASES)
+def test_plain_fuse_fwd_bwd(ops, H, ns_r, ns_d, drop, misalign):
+    N = 16
+    dsc = 1 / 0.9
+    rg_d, rg = _slabs(max(ns_r, 1), N, H, 1, misalign)
+    if ns_r == 0:
+        rg_d, rg = rg_d[0], rg[0].relu()                    # a finished embedding (post ReLU)
+        rg_d.copy_(rg.cuda())
+    dp_d, dp = _slabs(ns_d, N, H, 2, misalign)
+    br, bd_ = 0.1 * rnd(H, seed=3), 0.1 * rnd(H, seed=4)
+    lg, lb = 1 + 0.2 * rnd(H, seed=5), 0.1 * rnd(H, seed=6)
+    g1, b1 = 1 + 0.2 * rnd(H, seed=7), 0.1 * rnd(H, seed=8)
+    tok = 0.3 * rnd(H, seed=9)
+    keep = keep_mask(2 * N, H, seed=10) if drop else None
+    kf = keep.double() * dsc if drop else torch.ones(2 * N, H, dtype=torch.float64)
+    # float64 restatement: x0 = embd_drop([rgb; dep] + tok), rows 2n (rgb token) and 2n + 1 (depth token)
+    r_pre = (rg.double().sum(0) + br.double()) if ns_r > 0 else rg.double()
+    r = r_pre.relu() if ns_r > 0 else r_pre
+    r = r.detach().requires_grad_(True)
+    dpre = (dp.double().sum(0) + bd_.double()).detach().requires_grad_(True)
+    lgd, lbd, g1d, b1d, tokd = dd(lg), dd(lb), dd(g1), dd(b1), dd(tok)
+    dln = ln64(dpre, lgd, lbd)
+    dep = dln.relu()
+    t_r, t_d = r + tokd, dep + tokd
+    x0 = torch.stack([t_r, t_d], 1).reshape(2 * N, H) * kf
+    h1 = ln64(x0, g1d, b1d)
+    m1 = x0.mean(-1)
+    r1 = 1 / torch.sqrt(x0.var(-1, unbiased=False) + EPS)
+    # kernel
+    f = lambda *s: torch.empty(*s, device="cuda")          # noqa: E731
+    rgb_out = rg_d if ns_r == 0 else f(N, H)
+    dep_pre, mean_d, rstd_d, dep_out, x0_k, h1_k, m1_k, r1_k = f(N, H), f(N), f(N), f(N, H), f(2 * N, H), f(2 * N, H), f(2 * N), f(2 * N)
+    ops.plain_fuse_fwd(rg_d, ns_r, d(br), dp_d, ns_d, d(bd_), d(lg), d(lb), d(tok), d(keep), dsc, d(g1), d(b1), rgb_out,
+                       dep_pre, mean_d, rstd_d, dep_out, x0_k, h1_k, m1_k, r1_k)
+    torch.cuda.synchronize()
+    tag = f"plain H{H} ns_r{ns_r} ns_d{ns_d} drop{int(drop)} mis{int(misalign)}"
+    close_rel(rgb_out, r.detach(), f"{tag}: rgb", rtol=1e-5)
+    close_rel(dep_pre, dpre.detach(), f"{tag}: dep_pre", rtol=1e-5)
+    close_rel(mean_d, dpre.detach().mean(-1), f"{tag}: mean_d", rtol=1e-4)
+    close_rel(rstd_d, 1 / torch.sqrt(dpre.detach().var(-1, unbiased=False) + EPS), f"{tag}: rstd_d", rtol=1e-4)
+    close_rel(dep_out, dep.detach(), f"{tag}: dep", rtol=1e-4)
+    close_rel(x0_k, x0.detach(), f"{tag}: x0", rtol=1e-4)
+    close_rel(m1_k, m1.detach(), f"{tag}: m1", rtol=1e-4)
+    close_rel(r1_k, r1.detach(), f"{tag}: r1", rtol=1e-4)
+    close_rel(h1_k, h1.detach(), f"{tag}: h1", rtol=1e-4)
+    # backward: d_h1 plus the residual gradient added to norm1's input gradient (before embd_drop), given and None
+    dh1, a1 = rnd(2 * N, H, seed=11), rnd(2 * N, H, seed=12)
+    for add in (a1, None):
+        obj = (h1 * dh1.double()).sum() + ((x0 * add.double()).sum() if add is not None else 0.0)
+        wrt = (r, dpre, g1d, b1d, lgd, lbd, tokd, t_r, t_d)
+        gr, gdp, gg1, gb1, glg, glb, gtok, gtr, gtd = torch.autograd.grad(obj, wrt, retain_graph=True)
+        d_rgb_pre, d_dep_pre, t_tok = f(N, H), f(N, H), f(N, H)
+        ws_n1, ws_dep = f(N, 2, H), f(N, 2, H)
+        ops.plain_fuse_bwd(d(dh1), x0_k, m1_k, r1_k, d(g1), d(add), d(keep), dsc, rgb_out, dep_pre, mean_d, rstd_d, d(lg),
+                           d(lb), d_rgb_pre, d_dep_pre, ws_n1, ws_dep, t_tok)
+        # the t_tok-only mode (after the hidden-128 fuser chain): the same partials, bit for bit
+        t_only = torch.full((N, H), float("nan"), device="cuda")
+        ops.plain_fuse_bwd(d(dh1), x0_k, m1_k, r1_k, d(g1), d(add), d(keep), dsc, None, None, None, None, None, None, None,
+                           None, None, None, t_only)
+        torch.cuda.synchronize()
+        tg = f"{tag} add1{int(add is not None)}"
+        close_rel(d_rgb_pre, gr * (r.detach() > 0).double(), f"{tg}: d_rgb_pre", rtol=1e-3)
+        close_rel(d_dep_pre, gdp, f"{tg}: d_dep_pre", rtol=1e-3)
+        close_rel(ws_n1.sum(0)[0], gg1, f"{tg}: norm1 dgamma", rtol=1e-3)
+        close_rel(ws_n1.sum(0)[1], gb1, f"{tg}: norm1 dbeta", rtol=1e-3)
+        close_rel(ws_dep.sum(0)[0], glg, f"{tg}: depth LN dgamma", rtol=1e-3)
+        close_rel(ws_dep.sum(0)[1], glb, f"{tg}: depth LN dbeta", rtol=1e-3)
+        close_rel(t_tok, gtr + gtd, f"{tg}: t_tok (per frame)", rtol=1e-3)
+        close_rel(t_tok.double().sum(0), gtok, f"{tg}: d modality_token (column sum of t_tok)", rtol=1e-3)
+        assert torch.equal(t_only, t_tok), f"{tg}: t_tok-only mode differs from the full mode"
+
+
+def test_plain_fuse_refuses_a_row_past_its_seam_before_any_launch(ops, monkeypatch):
+    N, H = 4, 1032
+    f = lambda *s: torch.zeros(*s, device="cuda")          # noqa: E731
+
+    def launched(*a, **k):
+        raise AssertionError("the library was reached")
+    monkeypatch.setattr(ops._lib, "load", launched)
+    v, rows, rows2 = f(H), f(N, H), f(2 * N, H)
+    with pytest.raises(ValueError, match="plain fuser"):
+        ops.plain_fuse_fwd(rows, 0, v, rows, 1, v, v, v, v, None, 1.0, v, v, f(N, H), f(N, H), f(N), f(N), f(N, H), f(2 * N, H),
+                           f(2 * N, H), f(2 * N), f(2 * N))
+    with pytest.raises(ValueError, match="plain fuser"):
+        ops.plain_fuse_bwd(rows2, rows2, f(2 * N), f(2 * N), v, None, None, 1.0, rows, rows, f(N), f(N), v, v, f(N, H),
+                           f(N, H), f(N, 2, H), f(N, 2, H), f(N, H))
+    with pytest.raises(ValueError, match="plain fuser"):
+        ops.plain_fuse_bwd(rows2, rows2, f(2 * N), f(2 * N), v, None, None, 1.0, None, None, None, None, None, None, None,
+                           None, None, None, f(N, H))
+
+
+# ----------------------------------------------------------------------------------------------------------
 # decoder tail (tail.hip): norm3 -> decoder.norm -> heads, and its adjoint
 # ----------------------------------------------------------------------------------------------------------
 TAIL_SHAPES = [(1, 1), (6, 3), (7, 61), (18, 1000), (24, 3), (25, 61), (123, 1000)]        # (n_head, rows)

@@ -6,7 +6,10 @@ small or general kernel is decided inside the library, so the row's `attn` colum
 mha_small_ok, not observed), select the fp32 oracle's channels bit for bit, and match the fp64 oracle's
 outputs, fused tokens and losses within 1e-3 of scale and every gradient within 2e-3 (4e-3 with kink units excluded).
 Refused rows: the engine raises a ValueError naming the limit before anything is enqueued, and stays usable; train() with
-graph replay over a dataset holding a refused clip length raises before that shape is captured."""
+graph replay over a dataset holding a refused clip length raises before that shape is captured.
+Validation rows (VAL_CASES, VAL_CLIP_BOUNDS): validate()'s forward against the fp64 oracle's val forward, the channels that
+token fusion and the activation-magnitude fuser select from |x| column sums bit for bit against the fp32 oracle, the
+BN-blend fuser on running statistics far from the fresh state, and the longest forward-only clip and one frame past it."""
 import argparse
 import time
 
@@ -17,13 +20,15 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import futr_oracle as O, synth  # noqa: E402
+from tests import plain_oracle as PO  # noqa: E402
 from tests import vary_oracle as V  # noqa: E402
 from tests import width_cases as WC  # noqa: E402
 from tests.helpers import assert_close, ffn_kink_units, without_kink_units  # noqa: E402
 from tests.test_engine_gpu import close_rel  # noqa: E402
 
 ARGS = argparse.Namespace(input_dim=2048, seg=True, anticipate=True, max_pos_len=2000, input_type="i3d_transcript")
-MODELS = {"tf": "futr_safuser_tokenfusion", "vary": "futr_safuser_tokenfusion_vary", "bn": "futr_safuser_batchnormalization"}
+MODELS = {"tf": "futr_safuser_tokenfusion", "vary": "futr_safuser_tokenfusion_vary", "bn": "futr_safuser_batchnormalization",
+          "plain": "futr_safuser_depth"}
 
 
 def _cls(variant):
@@ -49,10 +54,17 @@ def build_model(variant, H, heads, K, p):
     return model.to("cuda")
 
 
-def bn_state(H):
+def bn_state(H, seed=None):
+    """The BatchNorm buffers: the fresh state (mean 0, var 1), or with a seed a state far from it (per-channel means and
+    variances that differ between the two BatchNorms, so a wrong buffer or channel index shows)."""
     st = {}
-    for pre in ("fuser.bn_rgb.", "fuser.bn_depth."):
-        st[pre + "running_mean"], st[pre + "running_var"] = torch.zeros(H, dtype=torch.float64), torch.ones(H, dtype=torch.float64)
+    for j, pre in enumerate(("fuser.bn_rgb.", "fuser.bn_depth.")):
+        if seed is None:
+            st[pre + "running_mean"], st[pre + "running_var"] = torch.zeros(H, dtype=torch.float64), torch.ones(H, dtype=torch.float64)
+        else:
+            g = torch.Generator().manual_seed(seed + j)
+            st[pre + "running_mean"] = (0.5 * torch.randn(H, generator=g)).float().double()
+            st[pre + "running_var"] = (0.25 + 2.0 * torch.rand(H, generator=g)).float().double()
         st[pre + "num_batches_tracked"] = torch.zeros((), dtype=torch.long)
     return st
 
@@ -63,7 +75,8 @@ def f64(batch):
 
 class Recorder:
     """Records the path-deciding launches of a step (the engine calls them as r3d_amd.ops attributes)."""
-    NAMES = ("embed_fuse_fwd", "token_exchange_fwd", "decoder_tail_losses", "decoder_tail_fwd", "mha_core_fwd", "check")
+    NAMES = ("embed_fuse_fwd", "token_exchange_fwd", "bn_blend_fwd", "scaled_exchange_fwd", "plain_fuse_fwd", "colabssum",
+             "token_select", "decoder_tail_losses", "decoder_tail_fwd", "mha_core_fwd", "check")
 
     def __init__(self, monkeypatch):
         from r3d_amd import ops
@@ -84,9 +97,21 @@ def oracle64(c, batch, p):
     """fp64 oracle (outputs, losses, gradients) and the fp32 oracle's channel selection."""
     b64 = f64(batch)
     K, heads = c.K, c.heads
+    if c.variant == "plain":                # (no selection: nothing for the fp32 oracle to decide)
+        t64 = PO.Trainer(p, K + 1, heads, 1, dtype=torch.float64, erank_weight=c.erank)
+        res, out, aux = t64.step(batch, apply=False)
+        if c.erank:
+            res["erank"] = aux["erank"]
+        return t64, res, out, aux, None
     if c.variant == "vary":
         t64 = V.Trainer(p, K + 1, heads, 1, dtype=torch.float64)
-        res, out, aux = t64.step(batch, apply=False)
+        if c.erank:                         # (as tests/test_vary_gpu.py's rank-penalty test)
+            out, aux = V.forward(t64.p, (b64[0], b64[2]), b64[1], "train", K + 1, heads, 1)
+            res = O.losses(out, b64[2], b64[3], b64[4], K + 1)
+            res["erank"] = O.effective_rank_torch(aux["fused"].reshape(-1, c.H))
+            (res["loss"] - c.erank * res["erank"]).backward()
+        else:
+            res, out, aux = t64.step(batch, apply=False)
         aux32 = V.Trainer(p, K + 1, heads, 1, dtype=torch.float32).step(batch, apply=False)[2]
         return t64, res, out, aux, aux32
     kw = dict(bn_state=bn_state(c.H), bn_training=True) if c.variant == "bn" else {}
@@ -117,7 +142,7 @@ def test_width_shape_against_fp64_oracle(c, oracle_lib, monkeypatch):
     batch = WC.make_batch(c)
     p = params(c.variant, H, heads, K)
     tr, res, oout, oaux, aux32 = oracle64(c, batch, p)
-    for k in ("idx_rgb", "idx_dep"):
+    for k in ("idx_rgb", "idx_dep") if aux32 is not None else ():
         assert np.array_equal(np.sort(np.asarray(aux32[k])), np.sort(np.asarray(oaux[k]))), \
             f"{cid}: fp32 and fp64 oracles select different {k}"
     t_oracle = time.time() - t0
@@ -139,8 +164,10 @@ def test_width_shape_against_fp64_oracle(c, oracle_lib, monkeypatch):
     # ---- the path the row states
     names = rec.names()
     assert not eng._chain_ok(w) and not eng._dec_chain_ok(w), cid
-    assert ("embed_fuse_fwd" in names) == c.seam, (cid, names)
+    seams = {n for n in names if n in WC.SEAMS.values()}
+    assert seams == ({WC.SEAMS[c.variant]} if c.seam else set()), (cid, names)          # exactly the row's own seam
     assert ("token_exchange_fwd" in names) == (c.variant == "tf" and not c.seam), (cid, names)
+    assert ("colabssum" in names) == (c.variant == "vary"), (cid, names)     # train mode: only vary scores from |x|
     assert tail_deferred == c.tail1 and ("decoder_tail_losses" in names) == c.tail1, (cid, tail_deferred)
     assert ("decoder_tail_fwd" in names) == (not c.tail1), cid
     ca = [a for n, a in rec.calls if n == "mha_core_fwd" and a[7] == WC.Q and a[8] == S]
@@ -151,8 +178,11 @@ def test_width_shape_against_fp64_oracle(c, oracle_lib, monkeypatch):
     assert eng._multi_stream() == c.side, cid
     # ---- selection, outputs, losses, gradients
     idx = eng.last["idx"]
-    assert np.array_equal(np.sort(idx[0].cpu().numpy()), np.sort(np.asarray(aux32["idx_rgb"]))), cid
-    assert np.array_equal(np.sort(idx[1].cpu().numpy()), np.sort(np.asarray(aux32["idx_dep"]))), cid
+    if c.variant == "plain":
+        assert idx is None, cid
+    else:
+        assert np.array_equal(np.sort(idx[0].cpu().numpy()), np.sort(np.asarray(aux32["idx_rgb"]))), cid
+        assert np.array_equal(np.sort(idx[1].cpu().numpy()), np.sort(np.asarray(aux32["idx_dep"]))), cid
     out = dict(seg=w.seg.view(B, S, K), action=w.actdur[:, :K].reshape(B, WC.Q, K),
                duration=w.actdur[:, K].reshape(B, WC.Q))
     for k in ("action", "duration", "seg"):
@@ -178,7 +208,109 @@ def test_width_shape_against_fp64_oracle(c, oracle_lib, monkeypatch):
             close_rel(g, r, f"{cid}/grad {n}" + (f" (kink units {sorted(kink)} excluded)" if kink else ""), rtol=rtol)
         n_grads += 1
     assert n_grads == len(eng.arena.live_names)
+    if c.variant == "plain":
+        assert "fuser.modality_token" in eng.arena.live_names, cid
     print(f"[width] {cid}: oracle {t_oracle:.1f} s, total {time.time() - t0:.1f} s")
+
+
+def val_oracle(variant, p, batch, K, heads, st, dtype):
+    """The oracle's validation forward (dropout off, no key padding mask) in `dtype`: (outputs, aux)."""
+    q = {n: v.to(dtype) for n, v in p.items()}
+    feats, depth, lab = batch[0].to(dtype), batch[1].to(dtype), batch[2]
+    with torch.no_grad():
+        if variant == "plain":
+            return PO.forward(q, feats, depth, "val", K + 1, heads, 1)               # the bare tensor, as validate() passes
+        if variant == "vary":
+            return V.forward(q, (feats, lab), depth, "val", K + 1, heads, 1)
+        kw = {}
+        if variant == "bn":
+            kw = dict(bn_state={k: v.to(dtype) if v.is_floating_point() else v.clone() for k, v in st.items()},
+                      bn_training=False)
+        return O.forward(q, (feats, lab), depth, "val", K + 1, heads, 1, **kw)
+
+
+def _val_model(variant, H, heads, K, p, st):
+    model = build_model(variant, H, heads, K, p).eval()
+    if st is not None:                      # running statistics far from the fresh state
+        sd = {k: v.float() if v.is_floating_point() else v for k, v in st.items()}
+        model.load_state_dict(sd, strict=False)
+        assert torch.equal(model.fuser.bn_depth.running_var.cpu(), sd["fuser.bn_depth.running_var"])
+    return model
+
+
+def _check_val(variant, c, batch, p, st, model, rec, tag):
+    """validate()'s own forward against the fp64 oracle; for the selecting variants the fp32 oracle's channels, bit for bit."""
+    B, S, K = c.B, c.S, c.K
+    oout, oaux = val_oracle(variant, p, batch, K, c.heads, st, torch.float64)
+    eng = model.engine()
+    d = [t.cuda() for t in batch]
+    out = eng.forward(d[0], d[1], d[2], "val", training=False, need_grad=False)
+    out = {k: v.clone() for k, v in out.items()}
+    torch.cuda.synchronize()
+    names = rec.names()
+    assert not eng._chain_ok(eng.last["w"]), tag
+    if variant in ("tf", "vary"):           # the seam is train mode only: |x| column sums, then the selection from them
+        assert "colabssum" in names and "embed_fuse_fwd" not in names, (tag, names)
+        _, aux32 = val_oracle(variant, p, batch, K, c.heads, st, torch.float32)
+        for j, k in enumerate(("idx_rgb", "idx_dep")):
+            assert np.array_equal(np.sort(np.asarray(aux32[k])), np.sort(np.asarray(oaux[k]))), \
+                f"{tag}: fp32 and fp64 oracles select different {k} (reseed the row)"
+            assert np.array_equal(eng.last["idx"][j].cpu().numpy(), np.sort(np.asarray(aux32[k]))), (tag, k)
+    else:
+        assert "colabssum" not in names, (tag, names)
+        assert ({n for n in names if n in WC.SEAMS.values()} == {WC.SEAMS[variant]}), (tag, names)
+    for k in ("action", "duration", "seg"):
+        close_rel(out[k], oout[k], f"{tag}/val {k}")
+    return out
+
+
+@pytest.mark.parametrize("v", WC.VAL_CASES, ids=WC.val_id)
+def test_val_forward_against_fp64_oracle(v, oracle_lib, monkeypatch):
+    t0 = time.time()
+    variant, H, heads = v
+    c = WC._c(2, 16, H, heads, variant=variant, pad="none")
+    tag = WC.val_id(v)
+    batch = WC.make_batch(c)
+    p = params(variant, H, heads, c.K)
+    st = bn_state(H, seed=H) if variant == "bn" else None
+    model = _val_model(variant, H, heads, c.K, p, st)
+    rec = Recorder(monkeypatch)
+    out = _check_val(variant, c, batch, p, st, model, rec, tag)
+    monkeypatch.undo()
+    if variant == "plain":                  # the bare features and the (features, labels) tuple: the same forward
+        d = [t.cuda() for t in batch]
+        with torch.no_grad():
+            bare = model(d[0], d[1], mode="val")
+            tup = model((d[0], d[2]), d[1], mode="val")
+        torch.cuda.synchronize()
+        for k in ("action", "duration", "seg"):
+            assert torch.equal(bare[k], tup[k]), (tag, k)
+            assert torch.equal(bare[k], out[k]), (tag, k)
+    if variant == "bn":                     # the eval state reads the running statistics and leaves them as they were
+        assert torch.equal(model.fuser.bn_rgb.running_mean.cpu(), st["fuser.bn_rgb.running_mean"].float())
+    print(f"[width] val {tag}: total {time.time() - t0:.1f} s")
+
+
+@pytest.mark.parametrize("H,heads,last,first,limit", WC.VAL_CLIP_BOUNDS)
+def test_val_forward_at_the_longest_forward_only_clip(H, heads, last, first, limit, oracle_lib, monkeypatch):
+    """The longest clip a forward alone admits runs against the fp64 oracle; one frame more raises a ValueError naming the
+    limit before anything is enqueued, and the engine is still usable."""
+    from r3d_amd import engine as E
+    t0 = time.time()
+    assert min(E.max_clip_len(H, heads, WC.Q, ARGS.max_pos_len, False), ARGS.max_pos_len) == last
+    c = WC._c(1, last, H, heads, pad="none")
+    batch = WC.make_batch(c)
+    p = params("tf", H, heads, c.K)
+    model = _val_model("tf", H, heads, c.K, p, None)
+    eng = model.engine()
+    big = [t.cuda() for t in WC.make_batch(WC._c(1, first, H, heads, pad="none"))]
+    rec = Recorder(monkeypatch)
+    with pytest.raises(ValueError, match=limit):
+        eng.forward(big[0], big[1], big[2], "val", training=False, need_grad=False)
+    assert not rec.calls and not eng.shapes, rec.names()
+    del big
+    _check_val("tf", c, batch, p, None, model, rec, f"H{H}x{heads}-S{last}")
+    print(f"[width] val H{H}x{heads} S{last}: total {time.time() - t0:.1f} s")
 
 
 @pytest.mark.parametrize("c", [c for c in REFUSED if WC.engine_refused(c)], ids=WC.case_id)
@@ -207,7 +339,7 @@ def test_refused_clip_lengths_raise_before_any_launch(c, monkeypatch):
     assert not rec.calls, rec.names()
     assert not eng.shapes
     monkeypatch.undo()
-    small = [t.cuda() for t in WC.make_batch(WC._c(1, 24, c.H, c.heads, pad="none"))]
+    small = [t.cuda() for t in WC.make_batch(WC._c(1, 24, c.H, c.heads, variant=c.variant, pad="none"))]
     got = [x.clone() for x in eng.train_step(*small, 1e-3, 5e-3)] + [eng.arena.params.clone()]
     fresh = build_model(c.variant, c.H, c.heads, c.K, p).train().engine()
     want = [x.clone() for x in fresh.train_step(*small, 1e-3, 5e-3)] + [fresh.arena.params.clone()]
