@@ -523,6 +523,14 @@ int r3d_losses_fwd_bwd(const float* seg_logits, int ld_seg, const float* act_log
  * the single-launch reduction, which every call leaves at zero).  tick_a / tick_b: optional device int64 counters
  * incremented once per call (the engine's step counter and dropout offset). */
 int64_t r3d_losses_ws_floats(int B, int S, int Q);
+/* The same launch with seg logits of Kseg classes (the RNN baseline's fc_seg has n_class - 1 outputs, model/rnn.py:37):
+ * ld_seg / ld_dseg >= Kseg, seg labels outside [0, Kseg) are ignored.  Kseg == K computes what r3d_losses_fwd_bwd does. */
+int r3d_losses_fwd_bwd_kseg(const float* seg_logits, int ld_seg, const float* act_logits, int ld_act, const float* dur,
+                            int ld_dur, const int64_t* past_label, const int64_t* target, const float* target_dur, int B,
+                            int S, int Q, int K, int Kseg, int pad_idx, int exclude_idx, int val_mode, const float* dur_den,
+                            float grad_scale, float* d_seg, int ld_dseg, float* d_act, int ld_dact, float* d_dur,
+                            int ld_ddur, float* loss_out, int64_t* counts, float* ws, int64_t* tick_a, int64_t* tick_b,
+                            void* stream);
 
 /* ---- training step only: the decoder's tail, the three losses and the tail's backward as ONE launch -------------------
  * = r3d_decoder_tail_fwd (transformer.py:329,182-183; futr_safuser_tokenfusion.py:219-226) -> r3d_losses_fwd_bwd
@@ -706,6 +714,23 @@ typedef struct r3d_clip_collate_job {
     float* features; float* depth; int64_t* past_label; float* trans_future_dur; int64_t* trans_future_target;
 } r3d_clip_collate_job;
 int r3d_clip_collate(const r3d_clip_collate_job* job, void* stream);
+
+/* ---- bidirectional LSTM layer (model/rnn.py:20,93: nn.LSTM(H, H/2, num_layers=2, bidirectional=True, batch_first=True))
+ * The recurrence of one layer, both directions in one launch (one workgroup per clip and direction, W_hh in registers).
+ * h = H / 2; rows are b-major (row = b * S + t); direction d (0 forward, 1 reverse) owns columns [4h d, 4h d + 4h) of the
+ * gate tensors and [h d, h d + h) of the state tensors.  Gate order i, f, g, o; h0 = c0 = 0; no packing, no masking.
+ * r3d_lstm_supported: 8 <= H <= 256, H % 8 == 0.
+ * r3d_lstm_layer_fwd: gin [B*S, 8h] = X W_ih^T + b_ih of both directions (the caller's GEMM); b_hh is added here.
+ *   Writes y [B*S, 2h] (the layer output), gates [B*S, 8h] (activated), cell [B*S, 2h] (c_t) and hprev [B*S, 2h]
+ *   (h_{t-1} in the direction's own order, zero at its first step, so that dW_hh = dG^T hprev per direction).
+ * r3d_lstm_layer_bwd: dy [B*S, 2h] = dL/d(layer output); writes dg [B*S, 8h] = dL/d(pre-activation gates).  Then
+ *   dW_ih = dG^T X, dW_hh(d) = dG(d)^T hprev(d), d b_ih = d b_hh = column sums of dG, dX = dG W_ih are the caller's GEMMs. */
+int r3d_lstm_supported(int H);
+int r3d_lstm_layer_fwd(const float* gin, int ldgin, const float* whh_fwd, const float* whh_rev, const float* bhh_fwd,
+                       const float* bhh_rev, float* y, int ldy, float* gates, int ldgates, float* cell, int ldcell,
+                       float* hprev, int ldhprev, int B, int S, int H, void* stream);
+int r3d_lstm_layer_bwd(const float* dy, int lddy, const float* whh_fwd, const float* whh_rev, const float* gates, int ldgates,
+                       const float* cell, int ldcell, float* dg, int lddg, int B, int S, int H, void* stream);
 
 #ifdef __cplusplus
 }

@@ -271,6 +271,11 @@ _SIGNATURES = {
     "r3d_erank_vt_polish": ([_P, _P, _P, _L, _P], C.c_int),
     "r3d_erank_plan": ([_I, _I, _I, _I, _P], C.c_int),
     "r3d_clip_collate": ([C.POINTER(ClipCollateJob), _P], C.c_int),
+    "r3d_losses_fwd_bwd_kseg": ([_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _I, _P, _I,
+                                 _P, _I, _P, _P, _P, _P, _P, _P], C.c_int),
+    "r3d_lstm_supported": ([_I], C.c_int),
+    "r3d_lstm_layer_fwd": ([_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_lstm_layer_bwd": ([_P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -125,6 +125,31 @@ R3D_EXPORT int r3d_losses_fwd_bwd(const float* seg_logits, int ld_seg, const flo
     return R3D_OK;
 }
 
+/* r3d_losses_fwd_bwd with seg logits of Kseg classes instead of K (the RNN baseline's fc_seg has n_class - 1 outputs,
+ * model/rnn.py:37); seg labels outside [0, Kseg) count as ignored, as labels outside [0, K) do in r3d_losses_fwd_bwd. */
+R3D_EXPORT int r3d_losses_fwd_bwd_kseg(const float* seg_logits, int ld_seg, const float* act_logits, int ld_act,
+                                       const float* dur, int ld_dur, const int64_t* past_label, const int64_t* target,
+                                       const float* target_dur, int B, int S, int Q, int K, int Kseg, int pad_idx,
+                                       int exclude_idx, int val_mode, const float* dur_den, float grad_scale, float* d_seg,
+                                       int ld_dseg, float* d_act, int ld_dact, float* d_dur, int ld_ddur, float* loss_out,
+                                       int64_t* counts, float* ws, int64_t* tick_a, int64_t* tick_b, void* stream) {
+    R3D_REQUIRE(act_logits && dur && past_label && target && target_dur && loss_out && counts && ws);
+    if (!r3d_aligned16(ws)) return R3D_EALIGN;
+    R3D_REQUIRE(B > 0 && S > 0 && Q > 0 && K > 0 && Kseg > 0);
+    R3D_REQUIRE(ld_act >= K && (!seg_logits || ld_seg >= Kseg) && ld_dur >= 1);
+    R3D_REQUIRE(!d_seg || (seg_logits && ld_dseg >= Kseg));
+    R3D_REQUIRE(!d_act || ld_dact >= K);
+    R3D_REQUIRE(!d_dur || ld_ddur >= 1);
+    LossArgs a{seg_logits, ld_seg, act_logits, ld_act, dur, ld_dur, past_label, target, target_dur, B, S, Q, K, pad_idx,
+               exclude_idx, val_mode, dur_den, grad_scale, d_seg, ld_dseg, d_act, ld_dact, d_dur, ld_ddur, loss_out,
+               counts, tick_a, tick_b, Kseg};
+    const int units = B * S + B * Q + B;
+    hipLaunchKernelGGL(losses_kernel, dim3(r3d_cdiv(units, 4)), dim3(256), 0, (hipStream_t)stream, a, ws,
+                       reinterpret_cast<unsigned*>(ws + 4 * (size_t)units));
+    R3D_LAUNCH_CHECK();
+    return R3D_OK;
+}
+
 /* Training step only: r3d_decoder_tail_fwd + r3d_losses_fwd_bwd + r3d_decoder_tail_bwd as one launch (see
  * tail_losses_kernel).  Supported when r3d_decoder_tail_losses_supported(...) != 0; ws as for r3d_losses_fwd_bwd. */
 R3D_EXPORT int r3d_decoder_tail_losses_supported(int H, int n_head, int Q, int rows) {

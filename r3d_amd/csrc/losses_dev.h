@@ -14,6 +14,7 @@ struct LossArgs {
     float* d_seg; int ld_dseg; float* d_act; int ld_dact; float* d_dur; int ld_ddur;
     float* loss_out; int64_t* counts;
     int64_t* tick_a; int64_t* tick_b;      // optional: ++*tick_a, ++*tick_b once per call (step counter, dropout offset)
+    int Kseg = 0;                          // classes of the seg logits when they differ from K (model/rnn.py:37: K - 1); 0: K
 };
 
 // CE of one row held across a wave.  Returns loss contribution; writes gradient (softmax - onehot) * gscale if dl.
@@ -67,9 +68,10 @@ __device__ __forceinline__ void losses_unit(const LossArgs& a, float* part, int 
         if (a.seg) {
             const int64_t lab = a.past_label[u];
             // labels outside [0,K) that are neither pad nor excluded would raise in PyTorch; here they are ignored
-            const bool valid = (lab != (int64_t)a.pad_idx) && (lab != (int64_t)a.exclude_idx) && lab >= 0 && lab < a.K;
+            const int Ks = a.Kseg > 0 ? a.Kseg : a.K;
+            const bool valid = (lab != (int64_t)a.pad_idx) && (lab != (int64_t)a.exclude_idx) && lab >= 0 && lab < Ks;
             int am;
-            float l = ce_row(a.seg + (size_t)u * a.ld_seg, a.K, lab, valid, a.pad_idx, a.grad_scale / (float)N,
+            float l = ce_row(a.seg + (size_t)u * a.ld_seg, Ks, lab, valid, a.pad_idx, a.grad_scale / (float)N,
                              a.d_seg ? a.d_seg + (size_t)u * a.ld_dseg : nullptr, lane, &am);
             if (valid && am == a.pad_idx) l += 2.0f;          // penalty term of cal_loss (utils.py:481-486)
             out_l = l; out_v = valid ? 1.f : 0.f; out_c = (valid && (int64_t)am == lab) ? 1.f : 0.f;

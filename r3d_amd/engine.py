@@ -125,9 +125,10 @@ class ParamArena:
     """Flat arenas; live parameters first (AdamW touches only that prefix), depth_projection.weight last among them
     so that everything else forms one contiguous all-reduce bucket that is ready before the big weight gradient."""
 
-    def __init__(self, named_params, device, extra_live=()):
+    def __init__(self, named_params, device, extra_live=(), live=None):
         named = list(named_params)
-        self.is_live = lambda n: is_live(n) or (bool(extra_live) and n.startswith(tuple(extra_live)))
+        # live: a model's own rule for the parameters that receive a gradient (default: the token-fusion model's + extra_live)
+        self.is_live = live if live is not None else (lambda n: is_live(n) or (bool(extra_live) and n.startswith(tuple(extra_live))))
         live = [(n, p) for n, p in named if self.is_live(n)]
         dead = [(n, p) for n, p in named if not self.is_live(n)]
 

@@ -864,6 +864,26 @@ def losses_fwd_bwd(seg, act, dur, ld_dur, past_label, target, target_dur, B, S, 
           "r3d_losses_fwd_bwd")
 
 
+def losses_fwd_bwd_kseg(seg, act, dur, ld_dur, past_label, target, target_dur, B, S, Q, K, Kseg, pad_idx, exclude_idx,
+                        loss_out, counts, *, val_mode=False, dur_den=None, grad_scale=1.0, d_seg=None, d_act=None, d_dur=None,
+                        ld_ddur=1, ws=None, tick_a=None, tick_b=None):
+    """losses_fwd_bwd with seg logits of Kseg classes (r3d_losses_fwd_bwd_kseg)."""
+    lib = _lib.load()
+    assert past_label.dtype == torch.int64 and target.dtype == torch.int64 and target_dur.dtype == torch.float32
+    assert past_label.is_contiguous() and target.is_contiguous() and target_dur.is_contiguous()
+    assert counts.dtype == torch.int64 and loss_out.dtype == torch.float32
+    need = lib.r3d_losses_ws_floats(B, S, Q)
+    if ws is None:
+        ws = torch.zeros(need, dtype=torch.float32, device=act.device)
+    assert ws.numel() >= need
+    check(lib.r3d_losses_fwd_bwd_kseg(_p(seg), _ld(seg) if seg is not None else 0, _p(act), _ld(act), _p(dur), ld_dur,
+                                      _p(past_label), _p(target), _p(target_dur), B, S, Q, K, Kseg, pad_idx, exclude_idx,
+                                      1 if val_mode else 0, _p(dur_den), grad_scale, _p(d_seg),
+                                      _ld(d_seg) if d_seg is not None else 0, _p(d_act), _ld(d_act) if d_act is not None else 0,
+                                      _p(d_dur), ld_ddur, _p(loss_out), _p(counts), _p(ws), _p(tick_a), _p(tick_b), _stream()),
+          "r3d_losses_fwd_bwd_kseg")
+
+
 def tail_losses_supported(H, n_head, Q, rows):
     return bool(_lib.load().r3d_decoder_tail_losses_supported(H, n_head, Q, rows))
 
@@ -1197,3 +1217,41 @@ def triple_mean_bwd(d_out, dy):
     N, Cc = d_out.shape
     assert tuple(dy.shape) == (3 * N, Cc) and dy.is_contiguous() and d_out.is_contiguous()
     check(_lib.load().r3d_triple_mean_bwd(_p(d_out), _p(dy), N, Cc, _stream()), "r3d_triple_mean_bwd")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# bidirectional LSTM layer (model/rnn.py)
+# ----------------------------------------------------------------------------------------------------------
+def lstm_supported(H):
+    """Whether the recurrence kernels take hidden H (= 2 x the LSTM hidden size of each direction)."""
+    return bool(_lib.load().r3d_lstm_supported(H))
+
+
+def lstm_layer_fwd(gin, whh_fwd, whh_rev, bhh_fwd, bhh_rev, y, gates, cell, hprev, B, S):
+    """gin [B*S, 4H] = X W_ih^T + b_ih of both directions -> y / cell / hprev [B*S, H], gates [B*S, 4H] (activated)."""
+    H = y.shape[1]
+    h = H // 2
+    for t_ in (gin, gates):
+        assert tuple(t_.shape) == (B * S, 8 * h)
+    for t_ in (y, cell, hprev):
+        assert tuple(t_.shape) == (B * S, 2 * h)
+    for w_ in (whh_fwd, whh_rev):
+        assert tuple(w_.shape) == (4 * h, h) and w_.is_contiguous()
+    for b_ in (bhh_fwd, bhh_rev):
+        assert b_.numel() == 4 * h and b_.is_contiguous()
+    check(_lib.load().r3d_lstm_layer_fwd(_p(gin), _ld(gin), _p(whh_fwd), _p(whh_rev), _p(bhh_fwd), _p(bhh_rev), _p(y), _ld(y),
+                                         _p(gates), _ld(gates), _p(cell), _ld(cell), _p(hprev), _ld(hprev), B, S, H, _stream()),
+          "r3d_lstm_layer_fwd")
+
+
+def lstm_layer_bwd(dy, whh_fwd, whh_rev, gates, cell, dg, B, S):
+    """dy [B*S, H] = dL/d(layer output) -> dg [B*S, 4H] = dL/d(pre-activation gates) of both directions."""
+    H = dy.shape[1]
+    h = H // 2
+    for t_ in (gates, dg):
+        assert tuple(t_.shape) == (B * S, 8 * h)
+    assert tuple(cell.shape) == (B * S, 2 * h) and tuple(dy.shape) == (B * S, 2 * h)
+    for w_ in (whh_fwd, whh_rev):
+        assert tuple(w_.shape) == (4 * h, h) and w_.is_contiguous()
+    check(_lib.load().r3d_lstm_layer_bwd(_p(dy), _ld(dy), _p(whh_fwd), _p(whh_rev), _p(gates), _ld(gates), _p(cell), _ld(cell),
+                                         _p(dg), _ld(dg), B, S, H, _stream()), "r3d_lstm_layer_bwd")

@@ -26,6 +26,8 @@ PRED_P = 0.5                                  # :236
 EXCLUDE_CLASS_IDX = 16                        # :319 (the 6th positional argument of weighted_accuracy_without_gif)
 DATASET_DIRS = dict(breakfast="breakfast", darai="darai", utkinects="utkinect")        # :223-230
 DATASET_DIRS["50salads"] = "50salads"
+NTU_EXCLUDE_CLASS_IDX = 120                   # evaluation/predict_nturgbd.py:330 (NTU's UNDEFINED)
+NTU_DATASET_DIRS = dict(DATASET_DIRS, nturgbd="nturgbd")                                # predict_nturgbd.py:231-232
 
 
 @torch.no_grad()
@@ -81,8 +83,9 @@ class DatasetFiles:
     """The reference's dataset layout under one root (:231-233): groundTruth/<video>.txt ('<image>,<L2 label>,<...>' per
     frame, :262-266), features_img/<video>.npy [T, 2048], features_depth/<video>.npy [T, ...]."""
 
-    def __init__(self, root):
-        self.gt, self.feat, self.depth = (os.path.join(root, d) for d in ("groundTruth", "features_img", "features_depth"))
+    def __init__(self, root, features_dir="features_img"):
+        # (features_dir: "features" in the NTU loop, predict_nturgbd.py:234)
+        self.gt, self.feat, self.depth = (os.path.join(root, d) for d in ("groundTruth", features_dir, "features_depth"))
 
     def exists(self, base):
         g, f, d = (os.path.exists(p) for p in self.paths(base))
@@ -106,12 +109,27 @@ def predict(model, vid_list, args, obs_p, n_class, actions_dict, device, data_pa
     """The reference's predict() (evaluation/predict_utkinects.py:215-396).  Returns (anticipation accuracy, segmentation
     accuracy) averaged over the videos.  details (optional list): receives one dict per video -- labels, the anticipated
     frame sequence and the per-horizon (true, false) class counts -- for tests and callers that want more than the prints."""
+    return _predict(model, vid_list, args, obs_p, n_class, actions_dict, device, data_path, log_dir, reader, details,
+                    EXCLUDE_CLASS_IDX, DATASET_DIRS, "features_img", True)
+
+
+def predict_nturgbd(model, vid_list, args, obs_p, n_class, actions_dict, device, data_path=None, log_dir=None, reader=None,
+                    details=None):
+    """The reference's evaluation/predict_nturgbd.py predict(): predict() with the excluded class 120 (:330), per-video
+    features under `features/` (:234), the `nturgbd` dataset directory (:231-232) and a model call without depth
+    (:305, the RNN model's forward(inputs, mode='test')).  The depth files are still looked up and read, as there."""
+    return _predict(model, vid_list, args, obs_p, n_class, actions_dict, device, data_path, log_dir, reader, details,
+                    NTU_EXCLUDE_CLASS_IDX, NTU_DATASET_DIRS, "features", False)
+
+
+def _predict(model, vid_list, args, obs_p, n_class, actions_dict, device, data_path, log_dir, reader, details, exclude_idx,
+             dataset_dirs, features_dir, with_depth):
     acc = seg_acc = 0.0
     idx = 0
     model.eval()
     if data_path is None:
-        data_path = os.path.join("./datasets", DATASET_DIRS.get(args.dataset, args.dataset))
-    files = reader if reader is not None else DatasetFiles(data_path)
+        data_path = os.path.join("./datasets", dataset_dirs.get(args.dataset, args.dataset))
+    files = reader if reader is not None else DatasetFiles(data_path, features_dir)
     sample_rate = args.sample_rate
     NONE = n_class - 1
     T_actions = np.zeros((len(EVAL_P), len(actions_dict)))
@@ -146,8 +164,11 @@ def predict(model, vid_list, args, obs_p, n_class, actions_dict, device, data_pa
                 label_base = past_seq[::sample_rate]
                 if log is not None:
                     log.write(f"\nimage base: \n{image_path[:past_len][::sample_rate]}\n")
-                outputs = model(inputs=(inputs.to(device).unsqueeze(0), None), depth_features=depth_in.to(device).unsqueeze(0),
-                                mode="test", epoch=idx, idx=obs_p)
+                if with_depth:
+                    outputs = model(inputs=(inputs.to(device).unsqueeze(0), None),
+                                    depth_features=depth_in.to(device).unsqueeze(0), mode="test", epoch=idx, idx=obs_p)
+                else:
+                    outputs = model(inputs=inputs.to(device).unsqueeze(0), mode="test", epoch=idx, idx=obs_p)
                 seg_label = outputs["seg"].reshape(-1, outputs["seg"].shape[-1]).max(-1)[1].cpu()
                 seg_one = normal_accuracy_without_gif(seg_label, label_base, actions_dict)
                 seg_acc += seg_one
@@ -155,7 +176,7 @@ def predict(model, vid_list, args, obs_p, n_class, actions_dict, device, data_pa
                 if log is not None:
                     log.write(f"{gt_file}\n------------------\n{len(past_seq)}\n")
                 ant_one = weighted_accuracy_without_gif(log, output_label[0], future_content, past_seq[-1], actions_dict,
-                                                        EXCLUDE_CLASS_IDX, label_base)
+                                                        exclude_idx, label_base)
                 acc += ant_one
                 idx += 1
                 # duration -> one label per anticipated frame (:322-353); queries from the first NONE on carry no duration

@@ -1,0 +1,162 @@
+"""Drop-in for the reference's ``train/train_unimodal.py`` (``from train_unimodal import train``, main_nturgbd.py:32):
+``train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed)``
+and ``validate(model, val_loader, criterion, pad_idx, device)`` with the reference's signatures, skip rules, loss
+composition, prints and checkpoint names, driving the RNN baseline (r3d_amd.model.rnn.FUTR).  Each batch is one replay of
+the fused step (forward + 3 losses + backward + AdamW, train_proposed_depth._GraphedSteps) with no device->host sync;
+epoch statistics are read back once per epoch.
+
+It is train_proposed_depth's loop except where the reference's differs (each can be checked against the cited line):
+  * the model is called without depth, ``model(inputs)`` (:186); the 5-tuple's depth tensor is never read or uploaded;
+  * the excluded class is 120 (NTU's UNDEFINED) for the seg, action and validation losses (:102,198,212);
+  * the per-epoch ``seg loss / seg acc`` line is printed (:245-248);
+  * ``model.train()`` runs after validate() (:270), so a later epoch trains in train mode (there is no dropout anyway);
+  * validate() calls the model in train mode with the (features, labels) tuple (:91).
+Kept from the shared loop: batches with fewer than 8 clips are skipped (:163), the epoch averages divide by (i + 1) (:234),
+validate() compares the normalised duration with the UNMASKED target and skips the seg loss (:86-113).  Multi-rank
+torch.distributed runs are refused (the reference's nn.DataParallel wrapper, main_nturgbd.py:131, is unwrapped).
+"""
+import os
+
+import torch
+import torch.distributed as dist
+
+from .model.rnn import FUTR
+from .optim import FlatAdamW
+from .engine_rnn import check_rnn_shape
+from .train_proposed_depth import _GraphedSteps, get_last_non_padding_labels, weighted_accuracy  # noqa: F401
+
+
+def _unwrap(model):
+    m = model
+    while hasattr(m, "module") and not isinstance(m, FUTR):
+        m = m.module
+    if not isinstance(m, FUTR):
+        raise TypeError("r3d_amd.train_unimodal drives r3d_amd.model.rnn.FUTR")
+    return m
+
+
+def _to_dev(data, device):
+    """(features, past_label, trans_dur_future, trans_future_target) on the device; the depth tensor stays where it is."""
+    features, _depth, past_label, trans_dur_future, trans_future_target = data
+    return (features.to(device=device, dtype=torch.float32).contiguous(), past_label.to(device).long().contiguous(),
+            trans_dur_future.to(device=device, dtype=torch.float32).contiguous(),
+            trans_future_target.to(device).long().contiguous())
+
+
+class _UnimodalSteps(_GraphedSteps):
+    """_GraphedSteps over the 4-tuple (features, past_label, trans_dur_future, trans_future_target): no depth buffer."""
+
+    def _enqueue(self, buf, lr, hyper, training):
+        eng = self.eng
+        feats, lab, dur, tgt = buf
+        wd, betas, eps = hyper
+        eng.forward(feats, None, lab, "train", training=training)
+        loss, counts = eng.losses(lab, tgt, dur, tick=True)
+        eng.backward()
+        eng.adamw(lr, wd, betas=betas, eps=eps, ticked=True)
+        self.acc_loss += loss
+        self.acc_cnt += counts
+
+
+def validate(model, val_loader, criterion, pad_idx, device):
+    core = _unwrap(model)
+    model.eval()
+    eng = core.engine()
+    val_loss = 0.0
+    val_class_correct = 0
+    val_class_total = 0
+    val_seg_correct = 0
+    val_seg_total = 0
+    val_weighted_accuracy_total = 0
+    with torch.no_grad():
+        for data in val_loader:
+            if data is None:
+                continue
+            features, past_label, trans_dur_future, trans_future_target = _to_dev(data, eng.device)
+            out = eng.forward(features, None, past_label, "train", training=False, need_grad=False)     # (:91)
+            loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, with_grad=False, val_mode=True)
+            lv, cv = loss.cpu(), counts.cpu()                       # one readback per validation clip
+            val_loss += float(lv[1] + lv[2])                        # action CE + duration (:104,112)
+            val_class_correct += int(cv[2])
+            val_class_total += int(cv[3])
+            val_weighted_accuracy_total += weighted_accuracy(
+                out["action"].reshape(-1, out["action"].size(-1)), trans_future_target.view(-1), pad_idx,
+                get_last_non_padding_labels(past_label, pad_idx))
+    val_loss /= len(val_loader)
+    val_accuracy = val_class_correct / val_class_total if val_class_total else 0
+    val_seg_accuracy = val_seg_correct / val_seg_total if val_seg_total else 0
+    val_weighted_accuracy = val_weighted_accuracy_total / len(val_loader)
+    print(f"Validation Loss: {val_loss:.3f}, Class Accuracy: {val_accuracy:.3f}, Segmentation Accuracy: "
+          f"{val_seg_accuracy:.3f}, Weighted Accuracy: {val_weighted_accuracy:.3f}")
+    return val_loss, val_accuracy, val_weighted_accuracy
+
+
+def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
+    core = _unwrap(model)
+    check_rnn_shape(core.hidden_dim, core.n_query, float(getattr(args, "erank_weight", 0.0) or 0.0))
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("r3d_amd.train_unimodal trains the RNN model on one GPU; multi-rank torch.distributed "
+                                  "runs of it are not supported")
+    model.to(device)
+    model.train()
+    eng = core.engine()
+    min_batch = getattr(args, "min_batch", 8)
+    print("Training Start")
+    best_val_loss = float("inf")
+    best_val_acc = 0
+    best_weight_acc = 0
+    acc_loss = torch.zeros(4, dtype=torch.float64, device=eng.device)
+    acc_cnt = torch.zeros(4, dtype=torch.int64, device=eng.device)
+    graphed = _UnimodalSteps(eng, acc_loss, acc_cnt) if getattr(args, "graph_steps", True) else None
+    for epoch in range(args.epochs):
+        acc_loss.zero_()
+        acc_cnt.zero_()
+        i = -1
+        for i, data in enumerate(train_loader):
+            if data is None:
+                continue
+            if len(data[0]) < min_batch:
+                continue
+            features, past_label, trans_dur_future, trans_future_target = _to_dev(data, eng.device)
+            g = optimizer.param_groups[0]
+            if graphed is not None and isinstance(optimizer, FlatAdamW):
+                graphed.step([features, past_label, trans_dur_future, trans_future_target], g["lr"],
+                             (g["weight_decay"], tuple(g["betas"]), g["eps"]), model.training)
+                continue
+            eng.forward(features, None, past_label, "train", training=model.training)
+            fused_opt = isinstance(optimizer, FlatAdamW)
+            loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, tick=fused_opt)
+            eng.backward()
+            if fused_opt:
+                eng.adamw(g["lr"], g["weight_decay"], betas=g["betas"], eps=g["eps"], ticked=True)
+            else:                                   # any other torch optimiser: expose the arena gradients to it
+                eng.arena.attach_grads(core.named_parameters())
+                optimizer.step()
+            acc_loss += loss
+            acc_cnt += counts
+        lsum, csum = acc_loss.cpu(), acc_cnt.cpu()                  # the single device->host read of the epoch
+        denom = i + 1                                                # the reference divides by (i+1), skipped or not
+        epoch_loss = float(lsum[3]) / denom if denom else 0.0
+        print("Epoch [", (epoch + 1), "/", args.epochs, "] Loss : %.3f" % epoch_loss)
+        if args.anticipate:
+            accuracy = int(csum[2]) / int(csum[3]) if int(csum[3]) else 0.0
+            print("Training Acc :%.3f" % accuracy, "CE loss :%.3f" % (float(lsum[1]) / denom if denom else 0.0))
+            if args.task == "long":
+                print("dur loss: %.5f" % (float(lsum[2]) / denom if denom else 0.0))
+        if args.seg:
+            acc_seg = int(csum[0]) / int(csum[1]) if int(csum[1]) else 0.0
+            print("seg loss :%.3f" % (float(lsum[0]) / denom if denom else 0.0), ", seg acc : %.5f" % acc_seg)
+        scheduler.step()
+        val_loss, val_acc, weight_acc = validate(model, val_loader, criterion, pad_idx, device)
+        if val_acc > best_val_acc or weight_acc > best_weight_acc:
+            best_val_loss, best_val_acc, best_weight_acc = val_loss, val_acc, weight_acc
+            save_path = os.path.join(model_save_path)
+            save_file = os.path.join(save_path, "seed_" + str(seed) + "_checkpoint" + str(epoch) + ".ckpt")
+            torch.save(model.state_dict(), save_file)
+            best_save_file = os.path.join(save_path, "seed_" + str(seed) + "_best.ckpt")
+            if os.path.exists(best_save_file):
+                os.remove(best_save_file)
+            torch.save(model.state_dict(), best_save_file)
+            print(f"Best model saved with validation loss: {best_val_loss:.3f}")
+        model.train()
+    return model
