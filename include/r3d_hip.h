@@ -732,6 +732,42 @@ int r3d_lstm_layer_fwd(const float* gin, int ldgin, const float* whh_fwd, const 
 int r3d_lstm_layer_bwd(const float* dy, int lddy, const float* whh_fwd, const float* whh_rev, const float* gates, int ldgates,
                        const float* cell, int ldcell, float* dg, int lddg, int B, int S, int H, void* stream);
 
+/* ---- temporal convolution (reference model/tcn.py: weight_norm(nn.Conv1d(C_in, C_out, 3, padding=2d, dilation=d)) + Chomp1d)
+ * Activations are [rows = B*S, C] row-major, a clip's S frames consecutive; tap j of weight_v [C_out, C_in, 3] reads frame
+ * t - (2 - j) d of the same clip (zeros before frame 0).  The three products are fp32-MFMA tile GEMMs whose operand loader
+ * applies the frame shift and the clip mask: no im2col copy exists.  Weight normalisation stays factored: s = g / |v|.
+ * r3d_tconv_supported: rows % S == 0, c_in and c_out multiples of 32, rows * max(c_in, c_out) < 2^31, rows <= 64 * 65535.
+ * r3d_tconv_wnorm: s[o] = g[o] / |v[o]|, inv_norm[o] = 1 / |v[o]| (norm over the C_in * 3 values, fixed order).
+ * r3d_tconv_fwd: P = X (*) v (raw, written when p_out != NULL); y = dropout(relu(s P + bias)) (drop: NULL or rows * c_out
+ *   keep-bytes); with out != NULL also out = relu(y + res) (the block's residual sum).
+ * r3d_tconv_bwd_prep: dz = (y > 0) ? drop_scale * dy : 0; d_bias = column sums of dz; d_g[o] = <dz[:, o], p[:, o]> inv_norm[o];
+ *   coef[o] = <dz[:, o], p[:, o]> inv_norm[o]^2.  ws: r3d_tconv_ws_floats(rows, c_out) floats (chunk partials, summed in order).
+ * r3d_tconv_dx: dx = sum_j shift_j(dz * s) v_j [+ res], zeroed where gate <= 0 (gate: NULL or the ReLU output below).
+ * r3d_tconv_wgrad: d_v = s (G - coef v) with G[o, c, j] = sum_r dz[r, o] x[r - (2 - j) d, c]; coef == NULL: d_v = G (s NULL: 1).
+ *   Long batches are cut into row ranges (one partial G each, summed range by range: one order); ws holds the partials,
+ *   r3d_tconv_wgrad_ws_floats(rows, c_in, c_out) floats (0: none needed, ws may be NULL).
+ * r3d_ce_rows_fwd_bwd: utils.py cal_loss without smoothing or excluded class over `rows` logit rows: loss_out[1] = loss_out[3]
+ *   = mean over ALL rows of (CE of the rows whose target != pad_idx) + 2 [argmax == pad_idx]; counts[2], counts[3] = correct,
+ *   total over those rows; d_logits (NULL: none) = d loss / d logits.  A target outside [0, C) is treated as padding.
+ *   One workgroup walks all rows (fixed order): sized for the B * 8 rows of this model, rows <= 65536, C <= 65536. */
+int r3d_tconv_supported(int rows, int S, int c_in, int c_out, int dilation);
+int64_t r3d_tconv_ws_floats(int rows, int c_out);
+int r3d_tconv_wnorm(const float* v, const float* g, int c_in, int c_out, float* s, float* inv_norm, void* stream);
+int r3d_tconv_fwd(const float* x, int ldx, const float* v, const float* s, const float* bias, int rows, int S, int c_in,
+                  int c_out, int dilation, float* p_out, int ldp, float* y, int ldy, const uint8_t* drop, float drop_scale,
+                  const float* res, int ldres, float* out, int ldout, void* stream);
+int r3d_tconv_bwd_prep(const float* dy, int lddy, const float* y, int ldy, const float* p, int ldp, float drop_scale,
+                       const float* inv_norm, int rows, int c_out, float* dz, int lddz, float* d_bias, float* d_g, float* coef,
+                       float* ws, void* stream);
+int r3d_tconv_dx(const float* dz, int lddz, const float* v, const float* s, int rows, int S, int c_in, int c_out, int dilation,
+                 const float* res, int ldres, const float* gate, int ldgate, float* dx, int lddx, void* stream);
+int r3d_tconv_wgrad(const float* dz, int lddz, const float* x, int ldx, const float* v, const float* s, const float* coef,
+                    int rows, int S, int c_in, int c_out, int dilation, float* d_v, float* ws, void* stream);
+int64_t r3d_tconv_wgrad_ws_floats(int rows, int c_in, int c_out);
+int r3d_ce_rows_supported(int rows, int C);
+int r3d_ce_rows_fwd_bwd(const float* logits, int ld, const int64_t* target, int rows, int C, int pad_idx, float* loss_out,
+                        int64_t* counts, float* d_logits, int ldd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -276,6 +276,16 @@ _SIGNATURES = {
     "r3d_lstm_supported": ([_I], C.c_int),
     "r3d_lstm_layer_fwd": ([_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
     "r3d_lstm_layer_bwd": ([_P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_tconv_supported": ([_I, _I, _I, _I, _I], C.c_int),
+    "r3d_tconv_ws_floats": ([_I, _I], C.c_int64),
+    "r3d_tconv_wnorm": ([_P, _P, _I, _I, _P, _P, _P], C.c_int),
+    "r3d_tconv_fwd": ([_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _F, _P, _I, _P, _I, _P], C.c_int),
+    "r3d_tconv_bwd_prep": ([_P, _I, _P, _I, _P, _I, _F, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P], C.c_int),
+    "r3d_tconv_dx": ([_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P], C.c_int),
+    "r3d_tconv_wgrad": ([_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),
+    "r3d_tconv_wgrad_ws_floats": ([_I, _I, _I], C.c_int64),
+    "r3d_ce_rows_supported": ([_I, _I], C.c_int),
+    "r3d_ce_rows_fwd_bwd": ([_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P], C.c_int),
 }
 
 EXPORTS = tuple(_SIGNATURES)

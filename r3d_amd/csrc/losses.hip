@@ -196,3 +196,68 @@ R3D_EXPORT int r3d_losses_finalize(const r3d_loss_finalize_job* job, void* strea
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }
+
+// ---- plain cal_loss over rows (reference utils.py:449-490 without smoothing, no excluded class): the TCN loop's loss ------
+// One workgroup; wave w takes rows w, w + 4, ...; per-wave sums in fp64, combined in wave order: one reduction order.
+namespace r3d {
+__global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ x, int ld, const int64_t* __restrict__ target,
+                                                     int rows, int C, int pad_idx, float* __restrict__ loss_out,
+                                                     int64_t* __restrict__ counts, float* __restrict__ dx, int lddx) {
+    __shared__ double red[4][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double lsum = 0.0;
+    int ncorrect = 0, ntotal = 0;
+    const float inv_rows = 1.0f / (float)rows;
+    for (int r = wave; r < rows; r += 4) {
+        const float* row = x + (size_t)r * ld;
+        float mx = -INFINITY;
+        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
+        mx = wave_max(mx);
+        float se = 0.f;
+        int first = 0x7fffffff;                       // torch.argmax: the first index of the maximum
+        for (int c = lane; c < C; c += 64) {
+            const float v = row[c];
+            se += __expf(v - mx);
+            if (v == mx && c < first) first = c;
+        }
+        se = wave_sum(se);
+        first = -(int)wave_max((float)(-first));      // indices < 2^24: exact in fp32
+        const int64_t t = target[r];
+        const bool live = t != pad_idx && t >= 0 && t < C;     // (a label outside the logits is skipped, never dereferenced)
+        const float lse = mx + __logf(se);
+        if (live) {
+            lsum += (double)(lse - row[t]) + (first == pad_idx ? 2.0 : 0.0);
+            ntotal += 1;
+            ncorrect += (first == (int)t);
+        }
+        if (dx) {
+            for (int c = lane; c < C; c += 64)
+                dx[(size_t)r * lddx + c] = live ? (__expf(row[c] - lse) - (c == (int)t ? 1.f : 0.f)) * inv_rows : 0.f;
+        }
+    }
+    if (lane == 0) { red[wave][0] = lsum; red[wave][1] = (double)ncorrect; red[wave][2] = (double)ntotal; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double l = ((red[0][0] + red[1][0]) + (red[2][0] + red[3][0])) / (double)rows;
+        loss_out[0] = 0.f;
+        loss_out[1] = (float)l;
+        loss_out[2] = 0.f;
+        loss_out[3] = (float)l;
+        counts[0] = 0;
+        counts[1] = 0;
+        counts[2] = (int64_t)(red[0][1] + red[1][1] + red[2][1] + red[3][1]);
+        counts[3] = (int64_t)(red[0][2] + red[1][2] + red[2][2] + red[3][2]);
+    }
+}
+}  // namespace r3d
+
+R3D_EXPORT int r3d_ce_rows_supported(int rows, int C) { return (rows >= 1 && rows <= (1 << 16) && C >= 1 && C <= (1 << 16)) ? 1 : 0; }
+
+R3D_EXPORT int r3d_ce_rows_fwd_bwd(const float* logits, int ld, const int64_t* target, int rows, int C, int pad_idx,
+                                   float* loss_out, int64_t* counts, float* d_logits, int ldd, void* stream) {
+    R3D_REQUIRE(logits && target && loss_out && counts && r3d_ce_rows_supported(rows, C) && ld >= C && (!d_logits || ldd >= C));
+    hipLaunchKernelGGL(r3d::ce_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, ld, target, rows, C, pad_idx,
+                       loss_out, counts, d_logits, ldd);
+    R3D_LAUNCH_CHECK();
+    return R3D_OK;
+}

@@ -1255,3 +1255,87 @@ def lstm_layer_bwd(dy, whh_fwd, whh_rev, gates, cell, dg, B, S):
         assert tuple(w_.shape) == (4 * h, h) and w_.is_contiguous()
     check(_lib.load().r3d_lstm_layer_bwd(_p(dy), _ld(dy), _p(whh_fwd), _p(whh_rev), _p(gates), _ld(gates), _p(cell), _ld(cell),
                                          _p(dg), _ld(dg), B, S, H, _stream()), "r3d_lstm_layer_bwd")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# dilated causal Conv1d with weight normalisation (model/tcn.py; csrc/tconv.hip) and the plain row cross-entropy
+# ----------------------------------------------------------------------------------------------------------
+def tconv_supported(rows, S, c_in, c_out, dilation):
+    """Whether the temporal-convolution kernels take [rows = B*S, c_in] -> [rows, c_out] at this dilation."""
+    return bool(_lib.load().r3d_tconv_supported(rows, S, c_in, c_out, dilation))
+
+
+def tconv_ws_floats(rows, c_out):
+    return int(_lib.load().r3d_tconv_ws_floats(rows, c_out))
+
+
+def _tconv_dims(v):
+    assert v.dim() == 3 and v.shape[2] == 3 and v.is_contiguous() and v.dtype == torch.float32
+    return v.shape[1], v.shape[0]
+
+
+def tconv_wnorm(v, g, s, inv_norm):
+    """s[o] = g[o] / |v[o]|, inv_norm[o] = 1 / |v[o]| for weight_v [C_out, C_in, 3], weight_g [C_out, 1, 1]."""
+    c_in, c_out = _tconv_dims(v)
+    assert g.numel() == c_out and s.numel() == c_out and inv_norm.numel() == c_out
+    check(_lib.load().r3d_tconv_wnorm(_p(v), _p(g), c_in, c_out, _p(s), _p(inv_norm), _stream()), "r3d_tconv_wnorm")
+
+
+def tconv_fwd(x, v, s, bias, S, dilation, y, *, p_out=None, drop_mask=None, drop_scale=1.0, res=None, out=None):
+    """y = dropout(relu(s * (x (*) v) + bias)); p_out: the raw product x (*) v; out = relu(y + res)."""
+    c_in, c_out = _tconv_dims(v)
+    rows = x.shape[0]
+    assert x.shape[1] == c_in and tuple(y.shape) == (rows, c_out) and (drop_mask is None or drop_mask.numel() == rows * c_out)
+    check(_lib.load().r3d_tconv_fwd(_p(x), _ld(x), _p(v), _p(s), _p(bias), rows, S, c_in, c_out, dilation, _p(p_out),
+                                    _ld(p_out) if p_out is not None else 0, _p(y), _ld(y), _p(drop_mask), drop_scale, _p(res),
+                                    _ld(res) if res is not None else 0, _p(out), _ld(out) if out is not None else 0, _stream()),
+          "r3d_tconv_fwd")
+
+
+def tconv_bwd_prep(dy, y, p, inv_norm, dz, d_bias, d_g, coef, ws, *, drop_scale=1.0):
+    """dz = (y > 0) ? drop_scale * dy : 0, d_bias, d_g = <dz, p> / |v|, coef = <dz, p> / |v|^2 (per output channel)."""
+    rows, c_out = dy.shape
+    assert ws.numel() >= tconv_ws_floats(rows, c_out) and y.shape == dy.shape == p.shape == dz.shape
+    check(_lib.load().r3d_tconv_bwd_prep(_p(dy), _ld(dy), _p(y), _ld(y), _p(p), _ld(p), drop_scale, _p(inv_norm), rows, c_out,
+                                         _p(dz), _ld(dz), _p(d_bias), _p(d_g), _p(coef), _p(ws), _stream()), "r3d_tconv_bwd_prep")
+
+
+def tconv_dx(dz, v, s, S, dilation, dx, *, res=None, gate=None):
+    """dx = sum_j shift_j(dz * s) v_j (+ res), zero where gate <= 0."""
+    c_in, c_out = _tconv_dims(v)
+    rows = dz.shape[0]
+    assert dz.shape[1] == c_out and tuple(dx.shape) == (rows, c_in)
+    check(_lib.load().r3d_tconv_dx(_p(dz), _ld(dz), _p(v), _p(s), rows, S, c_in, c_out, dilation, _p(res),
+                                   _ld(res) if res is not None else 0, _p(gate), _ld(gate) if gate is not None else 0, _p(dx),
+                                   _ld(dx), _stream()), "r3d_tconv_dx")
+
+
+def tconv_wgrad_ws_floats(rows, c_in, c_out):
+    return int(_lib.load().r3d_tconv_wgrad_ws_floats(rows, c_in, c_out))
+
+
+def tconv_wgrad(dz, x, v, S, dilation, d_v, *, s=None, coef=None, ws=None):
+    """d_v = s * (G - coef * v), G = the raw weight gradient of the effective weight; coef None: d_v = G.
+    ws: tconv_wgrad_ws_floats(rows, c_in, c_out) floats (the row-range partials of a long batch)."""
+    c_in, c_out = _tconv_dims(d_v)
+    rows = dz.shape[0]
+    assert dz.shape[1] == c_out and tuple(x.shape) == (rows, c_in) and (v is None or v.shape == d_v.shape)
+    need = tconv_wgrad_ws_floats(rows, c_in, c_out)
+    assert need == 0 or (ws is not None and ws.numel() >= need), "tconv_wgrad: workspace too small"
+    check(_lib.load().r3d_tconv_wgrad(_p(dz), _ld(dz), _p(x), _ld(x), _p(v), _p(s), _p(coef), rows, S, c_in, c_out, dilation,
+                                      _p(d_v), _p(ws), _stream()), "r3d_tconv_wgrad")
+
+
+def ce_rows_supported(rows, C):
+    return bool(_lib.load().r3d_ce_rows_supported(rows, C))
+
+
+def ce_rows_fwd_bwd(logits, target, pad_idx, loss_out, counts, d_logits=None):
+    """cal_loss (no smoothing, no excluded class) over the rows of logits [rows, C]: loss_out[1] = loss_out[3] = the loss,
+    counts[2:4] = (correct, total) over the rows whose target != pad_idx."""
+    rows, Cc = logits.shape
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == rows
+    assert loss_out.numel() == 4 and counts.numel() == 4 and counts.dtype == torch.int64
+    check(_lib.load().r3d_ce_rows_fwd_bwd(_p(logits), _ld(logits), _p(target), rows, Cc, pad_idx, _p(loss_out), _p(counts),
+                                          _p(d_logits), _ld(d_logits) if d_logits is not None else 0, _stream()),
+          "r3d_ce_rows_fwd_bwd")
