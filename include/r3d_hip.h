@@ -384,6 +384,27 @@ int r3d_mha_core_bwd(const float* q, int ldq, const float* k, int ldk, const flo
  * the launches apply: Lq * dh <= 1024 and the core's LDS (score matrix, its gradient, two key chunks) within 160 KiB. */
 int r3d_mha_core_supported(int Lq, int Lk, int dh, int bwd);
 
+/* ---- tiled attention core (csrc/attention_tiled.hip): the same product for long sequences -----------------------
+ * Operands, scale 1/sqrt(dh), key masks and the dropout keep-mask (uint8 [B][heads][Lq][Lk], applied with drop_scale to the
+ * normalised probabilities) exactly as r3d_mha_core_*, but no [Lq][Lk] tensor is written: the forward streams 64-key
+ * tiles under an online softmax and writes o and lse [B][heads][Lq] = log sum_j exp(s_ij) over the unmasked keys; the
+ * backward recomputes the probabilities from q, k, lse and the mask arguments (pass the forward's), needs the forward's
+ * o, and writes delta [B][heads][Lq] = rowsum(dO o O) into the caller's workspace.  Two backward kernels (one per query
+ * tile for dq, one per key tile for dk / dv), no atomics: results are bitwise reproducible.  No allocation, no host
+ * synchronisation.  A clip whose keys are all masked gives NaN rows, as r3d_mha_core_fwd does. */
+int r3d_mha_tiled_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                      const uint8_t* key_padding_mask, const int64_t* key_label, int pad_idx, const uint8_t* drop_mask,
+                      float drop_scale, float* o, int ldo, float* lse, int B, int heads, int Lq, int Lk, int dh,
+                      void* stream);
+int r3d_mha_tiled_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                      const uint8_t* key_padding_mask, const int64_t* key_label, int pad_idx, const uint8_t* drop_mask,
+                      float drop_scale, const float* o, int ldo, const float* lse, const float* d_o, int lddo, float* delta,
+                      float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, int B, int heads, int Lq, int Lk,
+                      int dh, void* stream);
+/* 1 if the two calls above run an (Lq, Lk, dh) problem, else 0; host-only, the same test the launches apply before they
+ * launch anything: Lq >= 1, Lk >= 1 and 1 <= dh <= 128 (forward and backward alike). */
+int r3d_mha_tiled_supported(int Lq, int Lk, int dh, int bwd);
+
 /* ---- fused decoder layer, one workgroup per clip (TransformerDecoderLayer.forward_post, model/extras/transformer.py:
  * 281-330; final decoder.norm :182-183; fc|fc_len head futr_safuser_tokenfusion.py:219-226) --------------------------
  * Replaces ~17 dependent launches per layer by one.  Supported when one clip's layer fits a CU's LDS

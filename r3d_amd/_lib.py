@@ -216,6 +216,10 @@ _SIGNATURES = {
     "r3d_mha_core_bwd": ([_P, _I, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
                          C.c_int),
     "r3d_mha_core_supported": ([_I, _I, _I, _I], C.c_int),
+    "r3d_mha_tiled_fwd": ([_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _F, _P, _I, _P, _I, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_mha_tiled_bwd": ([_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _F, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I,
+                           _I, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_mha_tiled_supported": ([_I, _I, _I, _I], C.c_int),
     "r3d_decoder_fused_supported": ([_I, _I, _I, _I], C.c_int),
     "r3d_decoder_layer_fwd": ([_P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P], C.c_int),
     "r3d_embed_fuse_fwd": ([_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I,

@@ -22,17 +22,30 @@ from .engine import ParamArena, DROP_P, EXCLUDE_CLASS_IDX, check_hidden
 
 # Shape admission (as engine.py's): every clip brings S queries, so both decoder attentions run Lq = Lk = S and the core's
 # limits (S * head width <= 1024 outputs per wave, S x S scores in 160 KiB of LDS) bound the clip length itself.  Checked on
-# the host before anything is enqueued; tests/test_query_admission_cpu.py pins them.
-def check_query_engine_shape(H, heads):
+# the host before anything is enqueued; tests/test_query_admission_cpu.py pins them.  long_clips (opts --long_clips, read by
+# the models into r3d_long_clips) adds the tiled core (csrc/attention_tiled.hip) for the shapes past those limits.
+def query_attention_route(S, H, heads, train, long_clips):
+    """The attention kernels both decoder attentions of an S-frame clip run through: "core" (r3d_mha_core_*, wherever it
+    admits the shape -- so a short clip launches the same kernels whatever the flag), "tiled" (r3d_mha_tiled_*, only with
+    long_clips) or None (refused)."""
+    dh = H // heads
+    if ops.mha_core_supported(S, S, dh, train):
+        return "core"
+    if long_clips and ops.mha_tiled_supported(S, S, dh, train):
+        return "tiled"
+    return None
+
+
+def check_query_engine_shape(H, heads, long_clips=False):
     """Raises ValueError unless the engine runs hidden H with `heads` attention heads at some training clip length."""
     check_hidden(H, heads)
     dh = H // heads
-    if not ops.mha_core_supported(1, 1, dh, True):                # (the bound only tightens as S grows)
+    if query_attention_route(1, H, heads, True, long_clips) is None:      # (the bound only tightens as S grows)
         raise ValueError(f"head width {dh} (hidden {H} / {heads} heads): no clip length trains -- the attention core's "
                          f"backward needs S * head width <= 1024 outputs per wave and its key chunks in 160 KiB of LDS")
 
 
-def check_query_clip_shape(S, H, heads, max_pos_len, train):
+def check_query_clip_shape(S, H, heads, max_pos_len, train, long_clips=False):
     """Raises ValueError unless a clip of S frames runs (train: with the backward, whose attention core needs more LDS).
     max_pos_len: the rows of pos_embedding (and, label-query, of positional_embedding_l3)."""
     if S <= 0:
@@ -40,18 +53,21 @@ def check_query_clip_shape(S, H, heads, max_pos_len, train):
     if S > max_pos_len:
         raise ValueError(f"clip length {S} > max_pos_len {max_pos_len}: the rows of the positional tables")
     dh = H // heads
-    if not ops.mha_core_supported(S, S, dh, train):
+    if query_attention_route(S, H, heads, train, long_clips) is None:
+        hint = ""
+        if not long_clips and ops.mha_tiled_supported(S, S, dh, train):
+            hint = " (the tiled core runs this shape: --long_clips)"
         raise ValueError(f"clip length {S} at head width {dh}: the decoder's attention cores run {S} queries x {S} keys, past "
                          f"the {'backward' if train else 'forward'} core's S * head width <= 1024 outputs per wave or its "
-                         f"S x S scores in 160 KiB of LDS")
+                         f"S x S scores in 160 KiB of LDS" + hint)
 
 
-def max_query_clip_len(H, heads, max_pos_len, train):
+def max_query_clip_len(H, heads, max_pos_len, train, long_clips=False):
     """The longest clip check_query_clip_shape admits (0: none; the bound tightens monotonically with S)."""
     lo, hi = 0, max_pos_len
     while lo < hi:
         mid = (lo + hi + 1) // 2
-        if ops.mha_core_supported(mid, mid, H // heads, train):
+        if query_attention_route(mid, H, heads, train, long_clips) is not None:
             lo = mid
         else:
             hi = mid - 1
@@ -80,9 +96,15 @@ class _Shape:
         self.dep_pre, self.dep, self.qpos = f(N, H), f(N, H), f(N, H)
         self.mean_d, self.rstd_d = f(N), f(N)
         self.tgt0 = torch.zeros(N, H, dtype=torch.float32, device=dev)
-        self.layers = [dict(sa_qkv=f(N, 3 * H), sa_o=f(N, H), p_sa=f(B, heads, S, S), t1_pre=f(N, H), t1=f(N, H), m1=f(N),
-                            r1=f(N), caq=f(N, H), cakv=f(N, 2 * H), ca_o=f(N, H), p_ca=f(B, heads, S, S), t2_pre=f(N, H),
-                            t2=f(N, H), m2=f(N), r2=f(N), ff1=f(N, 4 * H), t3_pre=f(N, H), t3=f(N, H), m3=f(N), r3=f(N))
+        self.route = query_attention_route(S, H, heads, train, eng.long_clips)
+        if self.route == "tiled":         # no [B, heads, S, S] probabilities: lse per attention, one delta workspace
+            att = lambda: dict(lse_sa=f(B, heads, S), lse_ca=f(B, heads, S))        # noqa: E731
+            self.delta = f(B, heads, S) if train else None
+        else:
+            att = lambda: dict(p_sa=f(B, heads, S, S), p_ca=f(B, heads, S, S))      # noqa: E731
+        self.layers = [dict(sa_qkv=f(N, 3 * H), sa_o=f(N, H), t1_pre=f(N, H), t1=f(N, H), m1=f(N),
+                            r1=f(N), caq=f(N, H), cakv=f(N, 2 * H), ca_o=f(N, H), t2_pre=f(N, H),
+                            t2=f(N, H), m2=f(N), r2=f(N), ff1=f(N, 4 * H), t3_pre=f(N, H), t3=f(N, H), m3=f(N), r3=f(N), **att())
                        for _ in range(L)]
         self.tgtF, self.mF, self.rF = f(N, H), f(N), f(N)
         self.pooled = f(BQ, H)
@@ -119,7 +141,8 @@ class UnsupDepthEngine:
         ops._lib.load()
         self.H, self.Q, self.K = module.hidden_dim, module.n_query, module.n_class
         self.heads, self.L = module.n_head, module.num_decoder_layers
-        check_query_engine_shape(self.H, self.heads)
+        self.long_clips = bool(getattr(module, "r3d_long_clips", False))       # (opts --long_clips: the tiled attention route)
+        check_query_engine_shape(self.H, self.heads, self.long_clips)
         self.dh = self.H // self.heads
         self.pad_idx = module.src_pad_idx
         # label_query: model/futr_proposed.py -- the decoder query is nn.Embedding(label indices) + a sinusoidal table
@@ -161,7 +184,7 @@ class UnsupDepthEngine:
     def _shape(self, B, S, train):
         key = (B, S, bool(train))
         if key not in self.shapes:
-            check_query_clip_shape(S, self.H, self.heads, self.max_pos_len, train)     # (before anything is enqueued)
+            check_query_clip_shape(S, self.H, self.heads, self.max_pos_len, train, self.long_clips)     # (before anything is enqueued)
             self.shapes[key] = _Shape(self, B, S, train)
         return self.shapes[key]
 
@@ -227,16 +250,24 @@ class UnsupDepthEngine:
             p = lambda n: a.p(pl + n)         # noqa: E731
             ops.gemm(GEMM_NT, tgt, p("self_attn.in_proj_weight"), c["sa_qkv"], a_add=w.qpos, a_add_mod=N,
                      bias=p("self_attn.in_proj_bias"), ws=ws)             # q = k = v = tgt + query_pos (:289)
-            ops.mha_core_fwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], c["sa_o"], B,
-                             heads, S, S, dh, drop_mask=dm(f"sa_p{l}"), drop_scale=dsc)
+            if w.route == "tiled":
+                ops.mha_tiled_fwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["sa_o"], c["lse_sa"],
+                                  B, heads, S, S, dh, drop_mask=dm(f"sa_p{l}"), drop_scale=dsc)
+            else:
+                ops.mha_core_fwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], c["sa_o"], B,
+                                 heads, S, S, dh, drop_mask=dm(f"sa_p{l}"), drop_scale=dsc)
             ops.gemm(GEMM_NT, c["sa_o"], p("self_attn.out_proj.weight"), c["t1_pre"], bias=p("self_attn.out_proj.bias"),
                      drop_mask=self._dm2(dm(f"d1_{l}"), N, H), drop_scale=dsc, res1=None if l == 0 else tgt, ws=ws)
             ops.layernorm_fwd(c["t1_pre"], p("norm1.weight"), p("norm1.bias"), c["t1"], c["m1"], c["r1"])
             wi, bi = p("multihead_attn.in_proj_weight"), p("multihead_attn.in_proj_bias")
             ops.gemm(GEMM_NT, c["t1"], wi[:H], c["caq"], a_add=w.qpos, a_add_mod=N, bias=bi[:H], ws=ws)
             ops.gemm(GEMM_NT, w.mem, wi[H:], c["cakv"], a_add=pos, a_add_mod=S, bias=bi[H:], ws=ws)   # k = v = memory + pos
-            ops.mha_core_fwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], c["ca_o"], B, heads, S, S, dh,
-                             key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=dm(f"ca_p{l}"), drop_scale=dsc)
+            if w.route == "tiled":
+                ops.mha_tiled_fwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["ca_o"], c["lse_ca"], B, heads, S, S, dh,
+                                  key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=dm(f"ca_p{l}"), drop_scale=dsc)
+            else:
+                ops.mha_core_fwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], c["ca_o"], B, heads, S, S, dh,
+                                 key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=dm(f"ca_p{l}"), drop_scale=dsc)
             ops.gemm(GEMM_NT, c["ca_o"], p("multihead_attn.out_proj.weight"), c["t2_pre"],
                      bias=p("multihead_attn.out_proj.bias"), drop_mask=self._dm2(dm(f"d2_{l}"), N, H), drop_scale=dsc,
                      res1=c["t1"], ws=ws)
@@ -252,7 +283,7 @@ class UnsupDepthEngine:
         # ---- adaptive average pooling of the S outputs to n_query rows (:134) + anticipation heads (:140-144)
         ops.avgpool_rows_fwd(w.tgtF, w.pooled, B, S, Q)
         ops.gemm(GEMM_NT, w.pooled, self.w_head, w.actdur, bias=self.b_head, ws=ws)
-        self.last = dict(w=w, x_rgb=x_rgb, x_dep=x_dep, drop=drop, mode=mode, tp=None)
+        self.last = dict(w=w, x_rgb=x_rgb, x_dep=x_dep, drop=drop, mode=mode, tp=None, key_labels=key_labels)
         return dict(seg=w.seg.view(B, S, self.Kseg), action=w.actdur[:, :K].view(B, Q, K), duration=w.actdur[:, K].view(B, Q))
 
     # ------------------------------------------------------------------------------------------------------
@@ -318,8 +349,13 @@ class UnsupDepthEngine:
                    dx2=gl["cap"], drop_mask=dm(f"d2_{l}", N, H), drop_scale=dsc)
             wgrad(gl["cap"], c["ca_o"], g("multihead_attn.out_proj.weight"), g("multihead_attn.out_proj.bias"))
             ops.gemm(GEMM_NN, gl["cap"], p("multihead_attn.out_proj.weight"), gl["cao"], ws=ws)
-            ops.mha_core_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], gl["cao"], gl["caq"], gl["cakv"][:, :H],
-                             gl["cakv"][:, H:], B, heads, S, S, dh, drop_mask=dmf(f"ca_p{l}"), drop_scale=dsc)
+            if w.route == "tiled":        # (the probabilities are recomputed: the forward's key mask again)
+                ops.mha_tiled_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["ca_o"], c["lse_ca"], gl["cao"], w.delta,
+                                  gl["caq"], gl["cakv"][:, :H], gl["cakv"][:, H:], B, heads, S, S, dh,
+                                  key_labels=st["key_labels"], pad_idx=self.pad_idx, drop_mask=dmf(f"ca_p{l}"), drop_scale=dsc)
+            else:
+                ops.mha_core_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], gl["cao"], gl["caq"], gl["cakv"][:, :H],
+                                 gl["cakv"][:, H:], B, heads, S, S, dh, drop_mask=dmf(f"ca_p{l}"), drop_scale=dsc)
             wi = p("multihead_attn.in_proj_weight")
             gwi, gbi = g("multihead_attn.in_proj_weight"), g("multihead_attn.in_proj_bias")
             wgrad(gl["cakv"], w.mem, gwi[H:], gbi[H:], b_add=pos, b_add_mod=S)
@@ -330,9 +366,14 @@ class UnsupDepthEngine:
                    dy2=gl["t2pre"], dx2=gl["sap"], drop_mask=dm(f"d1_{l}", N, H), drop_scale=dsc)
             wgrad(gl["sap"], c["sa_o"], g("self_attn.out_proj.weight"), g("self_attn.out_proj.bias"))
             ops.gemm(GEMM_NN, gl["sap"], p("self_attn.out_proj.weight"), gl["sao"], ws=ws)
-            ops.mha_core_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], gl["sao"],
-                             gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], B, heads, S, S, dh,
-                             drop_mask=dmf(f"sa_p{l}"), drop_scale=dsc)
+            if w.route == "tiled":
+                ops.mha_tiled_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["sa_o"], c["lse_sa"],
+                                  gl["sao"], w.delta, gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], B,
+                                  heads, S, S, dh, drop_mask=dmf(f"sa_p{l}"), drop_scale=dsc)
+            else:
+                ops.mha_core_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], gl["sao"],
+                                 gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], B, heads, S, S, dh,
+                                 drop_mask=dmf(f"sa_p{l}"), drop_scale=dsc)
             wgrad(gl["saqkv"], tgt_in, g("self_attn.in_proj_weight"), g("self_attn.in_proj_bias"), b_add=w.qpos, b_add_mod=N)
             ops.gemm(GEMM_NN, gl["saqkv"], p("self_attn.in_proj_weight"), gl["sain"], ws=ws)      # d (tgt_in + query_pos)
             # d query_pos += caqin + sain  (the query is an activation here: its gradient reaches the depth projection)

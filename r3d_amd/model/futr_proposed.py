@@ -34,6 +34,7 @@ class FUTR(nn.Module):
         self.num_decoder_layers = num_decoder_layers
         self.n_query = n_query
         self.args = args
+        self.r3d_long_clips = bool(getattr(args, "long_clips", False))    # (opts --long_clips: engine_unsup's tiled route)
         if getattr(args, "input_type", "i3d_transcript") != "i3d_transcript":
             raise NotImplementedError("only input_type='i3d_transcript' is built (futr_proposed.py:57-59,93-95: 'gt' embedding)")
         if not (getattr(args, "seg", True) and getattr(args, "anticipate", True)):

@@ -649,6 +649,29 @@ def mha_core_bwd(q, k, v, probs, d_o, dq, dk, dv, B, heads, Lq, Lk, dh, *, drop_
                                _stream()), "r3d_mha_core_bwd")
 
 
+def mha_tiled_supported(Lq, Lk, dh, bwd):
+    """mha_tiled_fwd (bwd False) / mha_tiled_bwd (bwd True) runs an (Lq, Lk, dh) problem: the launches' own check."""
+    return bool(_lib.load().r3d_mha_tiled_supported(Lq, Lk, dh, 1 if bwd else 0))
+
+
+def mha_tiled_fwd(q, k, v, o, lse, B, heads, Lq, Lk, dh, *, kpm=None, key_labels=None, pad_idx=0, drop_mask=None,
+                  drop_scale=1.0):
+    """The tiled core (csrc/attention_tiled.hip): o and lse [B, heads, Lq]; no [Lq, Lk] tensor is written."""
+    lib = _lib.load()
+    check(lib.r3d_mha_tiled_fwd(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(kpm), _p(key_labels), pad_idx, _p(drop_mask),
+                                drop_scale, _p(o), _ld(o), _p(lse), B, heads, Lq, Lk, dh, _stream()), "r3d_mha_tiled_fwd")
+
+
+def mha_tiled_bwd(q, k, v, o, lse, d_o, delta, dq, dk, dv, B, heads, Lq, Lk, dh, *, kpm=None, key_labels=None, pad_idx=0,
+                  drop_mask=None, drop_scale=1.0):
+    """Adjoint of mha_tiled_fwd: the probabilities are recomputed, so the forward's masks are passed again; delta
+    [B, heads, Lq] is a workspace the call fills."""
+    lib = _lib.load()
+    check(lib.r3d_mha_tiled_bwd(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(kpm), _p(key_labels), pad_idx, _p(drop_mask),
+                                drop_scale, _p(o), _ld(o), _p(lse), _p(d_o), _ld(d_o), _p(delta), _p(dq), _ld(dq), _p(dk),
+                                _ld(dk), _p(dv), _ld(dv), B, heads, Lq, Lk, dh, _stream()), "r3d_mha_tiled_bwd")
+
+
 # ----------------------------------------------------------------------------------------------------------
 # fused decoder layer
 # ----------------------------------------------------------------------------------------------------------

@@ -64,3 +64,7 @@ parser.add_argument("--torch_collectives", action="store_true", default=False,
 parser.add_argument("--pixel_shard", action="store_true", default=False,
                     help="multi-GPU only: shard depth_projection.weight (and its AdamW state) over pixels across ranks "
                          "instead of all-reducing its gradient (r3d_amd/parallel.py); same mathematics")
+parser.add_argument("--long_clips", action="store_true", default=False,
+                    help="depth-query / label-query models: run the decoder attentions of clips past the attention core's "
+                         "limits through the tiled core (head width <= 128; the clip length is then bounded by max_pos_len "
+                         "alone).  Shorter clips launch the same kernels either way")
