@@ -789,6 +789,23 @@ int r3d_ce_rows_supported(int rows, int C);
 int r3d_ce_rows_fwd_bwd(const float* logits, int ld, const int64_t* target, int rows, int C, int pad_idx, float* loss_out,
                         int64_t* counts, float* d_logits, int ldd, void* stream);
 
+/* ---- streaming QR: the effective rank of a whole data set (qr_stream.hip) --------------------------------------------
+ * R [lanes, H, H] fp32, row-major, upper triangular (the strictly lower part stays zero): lanes independent accumulators
+ * with R^T R = sum X^T X over the rows folded in, never forming the square.  One workgroup per lane; every reduction has
+ * a fixed order, no atomics, no workgroup waits on another: the same (lanes, call sequence) gives the same bits.
+ * r3d_qr_append_supported: 1 <= H <= 2048.  r3d_qr_append_tile_rows: the rows of one LDS tile at width H (0: refused).
+ * r3d_qr_append: folds the rows of x [n, H] (row stride ldx >= H) in; lane g takes rows [g ceil(n / lanes), ...).
+ *   row_label (NULL: every row counts) and pad_idx as key_label / pad_idx of r3d_mha_tiled_fwd: a row whose label equals
+ *   pad_idx is staged as zeros, and a zero row changes nothing.  rows (NULL: not counted) int64 [lanes]: each lane adds
+ *   its count of valid rows to its own slot.  n = 0 is a no-op; 1 <= lanes <= 64.
+ * r3d_qr_merge: lane g + stride is folded into lane g (R and rows) for every g that is a multiple of 2 stride, in one
+ *   launch; stride = 1, 2, 4, ... < lanes leaves the total in lane 0.  The source lanes are left as they are. */
+int r3d_qr_append_supported(int H);
+int r3d_qr_append_tile_rows(int H);
+int r3d_qr_append(const float* x, int64_t ldx, int n, int H, const int64_t* row_label, int pad_idx, float* R, int64_t* rows,
+                  int lanes, void* stream);
+int r3d_qr_merge(float* R, int64_t* rows, int H, int lanes, int stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,10 @@ _SIGNATURES = {
     "r3d_tconv_wgrad_ws_floats": ([_I, _I, _I], C.c_int64),
     "r3d_ce_rows_supported": ([_I, _I], C.c_int),
     "r3d_ce_rows_fwd_bwd": ([_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P], C.c_int),
+    "r3d_qr_append_supported": ([_I], C.c_int),
+    "r3d_qr_append_tile_rows": ([_I], C.c_int),
+    "r3d_qr_append": ([_P, _L, _I, _I, _P, _I, _P, _P, _I, _P], C.c_int),
+    "r3d_qr_merge": ([_P, _P, _I, _I, _I, _P], C.c_int),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -415,6 +415,7 @@ class FusionEngine:
         self.tp = None                    # parallel.PixelShardedDepth: depth_projection tensor-parallel over pixels
         self._fw = None
         self.last = None
+        self.rank_stream = None           # [(workspace attribute, rankstream.StreamingRank)]: fed by every forward while set
         self._adam = None
         self._drop_ready = None           # workspace whose dropout pool already holds the masks of the next forward
         # high-water mark of the pos_embedding gradient rows a backward has written: a step only writes its first S rows
@@ -720,6 +721,11 @@ class FusionEngine:
         w._er_forked = False
         self.last = dict(w=w, x_rgb=x_rgb, x_dep=x_dep, mask=mask, idx=idx, drop=drop, mode=mode, tp=tp, seam=seam, erank=er,
                          paired=paired, bn_training=bool(fw.get("bn_training", False)))
+        if self.rank_stream is not None:
+            # the data-set rank (rankstream.py): this batch's embeddings and fused tokens folded into the streaming QR,
+            # padded frames (label == pad_idx) left out -- one launch each, enqueued behind the forward
+            for attr, acc in self.rank_stream:
+                acc.update(getattr(w, attr), labels, self.pad_idx if labels is not None else None)
         return dict(seg=w.seg.view(B, S, K), action=w.actdur[:, :K].view(B, Q, K), duration=w.actdur[:, K].view(B, Q))
 
     # ---- effective-rank penalty on the fused token matrix [N, H] (erank.hip; Appendix A.11) ------------------------------

@@ -1153,6 +1153,61 @@ def erank_vt_polish(vt_raw, gv, vt):
     check(lib.r3d_erank_vt_polish(_p(vt_raw), _p(gv), _p(vt), vt.numel(), _stream()), "r3d_erank_vt_polish")
 
 
+# ---- streaming QR (qr_stream.hip): the effective rank of a whole data set, r3d_amd/rankstream.py
+def qr_append_supported(H):
+    """r3d_qr_append takes rows of width H (host only)."""
+    return bool(_lib.load().r3d_qr_append_supported(H))
+
+
+def qr_append_tile_rows(H):
+    """Rows of one LDS tile of r3d_qr_append at width H (host only; 0 when H is refused)."""
+    return int(_lib.load().r3d_qr_append_tile_rows(H))
+
+
+def _qr_require(cond, msg):
+    if not cond:
+        raise ValueError(msg)
+
+
+def _qr_accumulators(R, rows):
+    _qr_require(R.dim() == 3 and R.shape[1] == R.shape[2] and R.is_contiguous() and R.dtype == torch.float32 and R.is_cuda,
+                "R must be a contiguous float32 device tensor [lanes, H, H]")
+    _qr_require(rows is None or (rows.dtype == torch.int64 and rows.is_cuda and rows.is_contiguous()
+                                 and rows.numel() == R.shape[0]), "rows must be a contiguous int64 device tensor [lanes]")
+    return R.shape[0], R.shape[1]
+
+
+def qr_append(x, R, *, rows=None, row_label=None, pad_idx=0):
+    """Folds the rows of x [n, H] (unit column stride, row stride >= H) into the accumulators R [lanes, H, H]; lane g takes
+    rows [g ceil(n / lanes), ...).  row_label int64 [n]: rows whose label equals pad_idx are left out; rows int64 [lanes]
+    gains each lane's count of valid rows.  Enqueue only.  A malformed tensor raises ValueError, a refused H / lanes / ldx
+    R3DHipError (R3D_EINVAL), both before any launch."""
+    lanes, H = _qr_accumulators(R, rows)
+    _qr_require(x.dim() == 2 and x.shape[1] == H, f"x must be [n, {H}], got {tuple(x.shape)}")
+    n = x.shape[0]
+    if n > 0:
+        _qr_require(x.dtype == torch.float32 and x.is_cuda, "x must be a float32 device tensor")
+        _qr_require(x.stride(1) == 1 or H == 1, "x needs unit column stride")
+    ldx = x.stride(0) if n > 1 else max(x.stride(0), H)
+    _qr_require(row_label is None or (row_label.dtype == torch.int64 and row_label.is_cuda and row_label.is_contiguous()
+                                      and row_label.numel() == n), f"row_label must be a contiguous int64 device tensor [{n}]")
+    check(_lib.load().r3d_qr_append(_p(x) if n > 0 else None, ldx, n, H, _p(row_label), int(pad_idx), _p(R), _p(rows), lanes,
+                                    _stream()), "r3d_qr_append")
+
+
+def qr_merge(R, rows=None):
+    """The merge tree over the lanes of R [lanes, H, H] (and of rows int64 [lanes]): ceil(log2 lanes) launches leave the
+    total in lane 0.  In place: the other lanes are left partly merged.  Enqueue only."""
+    lanes, H = _qr_accumulators(R, rows)
+    lib = _lib.load()
+    if lanes == 1:                     # (still validates H)
+        check(lib.r3d_qr_merge(_p(R), _p(rows), H, 1, 1, _stream()), "r3d_qr_merge")
+    stride = 1
+    while stride < lanes:
+        check(lib.r3d_qr_merge(_p(R), _p(rows), H, lanes, stride, _stream()), "r3d_qr_merge")
+        stride *= 2
+
+
 # ----------------------------------------------------------------------------------------------------------
 # depth-as-query model (model/futr_unsupervised_depth.py)
 # ----------------------------------------------------------------------------------------------------------

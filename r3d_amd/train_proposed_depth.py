@@ -356,8 +356,12 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     eng.defer_tail = True       # every step here is forward -> losses -> backward: tail forward, losses and tail backward
                                 # run as one launch (validate()'s forwards carry no gradient workspace and are unaffected)
     dp = None
-    if dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1
-                                                          or os.environ.get("R3D_REHEARSE_DIST") == "1"):
+    parallel = dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1
+                                                                  or os.environ.get("R3D_REHEARSE_DIST") == "1")
+    if getattr(args, "erank_report", False) and parallel:
+        raise ValueError("--erank_report under data parallelism: each rank validates a shard and the streaming QR's R is "
+                         "not merged across ranks; run the report on one GPU")
+    if parallel:
         # --pixel_shard: depth_projection tensor-parallel over pixels (parallel.PixelShardedDepth); per-rank batch sizes may
         # differ at the end of an epoch, so the row counts are exchanged every step
         dp = DataParallelStep(eng, pixel_shard=getattr(args, "pixel_shard", False), equal_batches=False)
@@ -366,6 +370,11 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     is_main = dp is None or dp.rank == 0
     min_batch = getattr(args, "min_batch", 8)
     erank_every = getattr(args, "erank_every", 0)
+    rank_accs = None
+    if getattr(args, "erank_report", False):
+        from . import rankstream
+        rank_accs = rankstream.attach(core)          # (ValueError for the query models: no fused token matrix)
+        rankstream.detach(core)                      # fed by validate()'s forwards only
     eng.erank_weight = float(getattr(args, "erank_weight", 0.0))
     print("Training Start")
     best_val_loss = float("inf")
@@ -483,7 +492,16 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         scheduler.step()
         if dp is not None and dp.tp is not None:
             dp.tp.sync_full_weight()                                 # validation and checkpoints see the complete weight
-        val_loss, val_acc, weight_acc = validate(model, val_loader, criterion, pad_idx, device)
+        if rank_accs is not None:
+            for acc in rank_accs.values():
+                acc.reset()
+            eng.rank_stream = [(rankstream.BUFFERS[name], acc) for name, acc in rank_accs.items()]
+        try:
+            val_loss, val_acc, weight_acc = validate(model, val_loader, criterion, pad_idx, device)
+        finally:
+            eng.rank_stream = None
+        if rank_accs is not None:
+            print(rankstream.report_line({name: acc.finalize() for name, acc in rank_accs.items()}))
         if getattr(args, "restore_train_mode", False):
             model.train()
         if (val_acc > best_val_acc or weight_acc > best_weight_acc) and is_main:
