@@ -806,6 +806,33 @@ int r3d_qr_append(const float* x, int64_t ldx, int n, int H, const int64_t* row_
                   int lanes, void* stream);
 int r3d_qr_merge(float* R, int64_t* rows, int H, int lanes, int stride, void* stream);
 
+/* ---- supervised contrastive loss (supcon.hip; reference loss/spc.py SupConLoss) -----------------------------------------
+ * x [N, D] fp32 (row stride ldx >= D): the contrast rows, view by view; row r carries labels[r mod bsz] (int64 [bsz];
+ * NULL: the sample index r mod bsz, the SimCLR case) and N is a multiple of bsz.  The first A rows are anchors (A = N:
+ * contrast_mode 'all', A = bsz: 'one').  With s_ij = x_i . x_j / temperature, C(i) = { j != i : row j not ignored },
+ * lse_i = log sum_{C(i)} exp s_ij, Pos(i) = { j in C(i) : y_j = y_i }, P_i = |Pos(i)|:
+ *   loss = sum over non-ignored anchors with P_i > 0 of -(temperature / base_temperature) (mean_{Pos(i)} s_ij - lse_i),
+ *          divided by max(1, number of non-ignored anchors n_a).
+ * A row is ignored when has_ignore != 0, labels != NULL and its label equals ignore_index: neither anchor nor contrast.
+ * A row with no admissible contrast (N = 1, everything else ignored) contributes 0.  normalize != 0: every row is divided
+ * by max(|x|, 1e-12) while it is staged (F.normalize); no normalised copy is written.  64 x 64 score tiles streamed through
+ * LDS under an online log-sum-exp that never includes the diagonal: no N x N tensor, fixed-order reductions, no atomics
+ * (the same call gives the same bits), no allocation, no host synchronisation.
+ * ws: r3d_supcon_ws_floats(N) floats owned by the caller: lse [N], positive mean [N], P [N], 1 / max(|x|, 1e-12) [N]
+ *   (1 without normalize) and n_a; the forward writes it, the backward reads it.  Rows >= A keep lse, mean and P unwritten.
+ * r3d_supcon_fwd: loss_out[0] = loss.
+ * r3d_supcon_bwd: the forward's arguments again; dx [N, D] (row stride lddx >= D) = (add != 0 ? dx : 0) + gscale * d_loss[0]
+ *   * d loss / d x, d_loss a device scalar (NULL: 1).  One launch, one sweep of the column tiles per 64-row tile.
+ * r3d_supcon_supported: 1 <= D <= 256 (host-only).  A refused shape returns R3D_EINVAL before anything is enqueued. */
+int r3d_supcon_supported(int D);
+int64_t r3d_supcon_ws_floats(int N);
+int r3d_supcon_fwd(const float* x, int ldx, const int64_t* labels, int bsz, int N, int A, int D, int has_ignore,
+                   int64_t ignore_index, float temperature, float base_temperature, int normalize, float* ws,
+                   float* loss_out, void* stream);
+int r3d_supcon_bwd(const float* x, int ldx, const int64_t* labels, int bsz, int N, int A, int D, int has_ignore,
+                   int64_t ignore_index, float temperature, float base_temperature, int normalize, const float* ws,
+                   const float* d_loss, float gscale, float* dx, int lddx, int add, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -294,6 +294,10 @@ _SIGNATURES = {
     "r3d_qr_append_tile_rows": ([_I], C.c_int),
     "r3d_qr_append": ([_P, _L, _I, _I, _P, _I, _P, _P, _I, _P], C.c_int),
     "r3d_qr_merge": ([_P, _P, _I, _I, _I, _P], C.c_int),
+    "r3d_supcon_supported": ([_I], C.c_int),
+    "r3d_supcon_ws_floats": ([_I], C.c_int64),
+    "r3d_supcon_fwd": ([_P, _I, _P, _I, _I, _I, _I, _I, _L, _F, _F, _I, _P, _P, _P], C.c_int),
+    "r3d_supcon_bwd": ([_P, _I, _P, _I, _I, _I, _I, _I, _L, _F, _F, _I, _P, _P, _F, _P, _I, _I, _P], C.c_int),
 }
 
 EXPORTS = tuple(_SIGNATURES)

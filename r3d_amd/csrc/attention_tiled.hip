@@ -17,11 +17,10 @@
 //     dkv     grid over KEY tiles (launched after dq: it reads delta): K / V resident, sweeps the query tiles with the
 //             TRANSPOSED products (K Q^T, V dO^T, so the key is the accumulator row): dV += P'^T dO, dK += dS^T Q.
 #include "common.h"
+#include "tile_mma.h"
 #include "../../include/r3d_hip.h"
 
 namespace r3d {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct TiledArgs {
     const float *q, *k, *v;
@@ -43,77 +42,10 @@ struct TiledArgs {
     float scale;
 };
 
-constexpr int TT = 64;          // tile rows (queries) and columns (keys)
-constexpr int SLD = TT + 4;     // score tile row stride: 16 rows x 4 lanes of a wave hit 64 distinct banks
-
-__device__ __forceinline__ float4 lds4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-// rows [row0, row0 + 64) x [0, dh) of a strided matrix -> LDS [64][DP + 4]; rows past L and columns past dh are zero.
-// 16-byte loads where the head's rows allow them (the engine's slices do), single floats otherwise (dh 5, odd offsets).
-template <int DP>
-__device__ __forceinline__ void stage_tile(float* dst, const float* base, int ld, int row0, int L, int dh, int tid) {
-    constexpr int LD = DP + 4;
-    if (((reinterpret_cast<uintptr_t>(base) & 15u) | (ld & 3) | (dh & 3)) == 0) {
-        for (int e = tid; e < TT * DP / 4; e += 256) {
-            const int r = e / (DP / 4), d = (e % (DP / 4)) * 4;
-            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row0 + r < L && d < dh) x = *reinterpret_cast<const float4*>(base + (size_t)(row0 + r) * ld + d);
-            *reinterpret_cast<float4*>(dst + r * LD + d) = x;
-        }
-        return;
-    }
-    for (int e = tid; e < TT * DP; e += 256) {
-        const int r = e / DP, d = e % DP;
-        float x = 0.f;
-        if (row0 + r < L && d < dh) x = base[(size_t)(row0 + r) * ld + d];
-        dst[r * LD + d] = x;
-    }
-}
-
-// acc[16 x 16] += A[16 rows][DP] . B[16 rows][DP]^T, both LDS row-major with stride DP + 4: row of acc <- row of A, column <- row of B
-template <int DP>
-__device__ __forceinline__ void mma_nt(f32x4& acc, const float* A, const float* Bm, int c, int kq) {
-    constexpr int LD = DP + 4;
-    const float* ap = A + c * LD + 4 * kq;
-    const float* bp = Bm + c * LD + 4 * kq;
-#pragma unroll
-    for (int k0 = 0; k0 < DP; k0 += 16) {
-        const float4 a = lds4(ap + k0), b = lds4(bp + k0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-    }
-}
-
-// acc[n] (16 x 16, columns [16n, 16n + 16)) += P[16 rows][64] . M[64 rows][DP]: P with stride SLD, M with stride DP + 4
-template <int DP>
-__device__ __forceinline__ void mma_nn(f32x4 (&acc)[DP / 16], const float* P, const float* M, int c, int kq) {
-    constexpr int LD = DP + 4;
-#pragma unroll
-    for (int j0 = 0; j0 < TT; j0 += 16) {
-        const float4 a = lds4(P + c * SLD + j0 + 4 * kq);
-        const float* mp = M + (j0 + 4 * kq) * LD + c;
-#pragma unroll
-        for (int n = 0; n < DP / 16; ++n) {
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, mp[16 * n], acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, mp[LD + 16 * n], acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, mp[2 * LD + 16 * n], acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, mp[3 * LD + 16 * n], acc[n], 0, 0, 0);
-        }
-    }
-}
-
 __device__ __forceinline__ bool key_masked(const TiledArgs& a, int b, int j) {
     if (j >= a.Lk) return true;
     const size_t e = (size_t)b * a.Lk + j;
     return (a.kpm && a.kpm[e]) || (a.key_label && a.key_label[e] == (int64_t)a.pad_idx);
-}
-
-__device__ __forceinline__ float quad_sum(float v) {       // over the 4 lanes of a row, fixed order
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    return v;
 }
 
 // accumulator tiles of wave w -> rows [row0 + 16w, ...) x [0, dh) of a strided matrix (rows past L are not written)

@@ -22,6 +22,8 @@ EXCLUDE_CLASS_IDX = 120         # NTU's UNDEFINED class, hard-coded at train/tra
 POOL_ROWS = 8                   # F.adaptive_avg_pool1d(tgt, 8) (model/rnn.py:97)
 RNN_MIN_H, RNN_MAX_H = 8, 256   # the recurrence kernels' range (csrc/lstm.hip: W_hh of one direction in registers)
 
+SUPCON_BASE_T = 0.07            # SupConLoss's default base_temperature (loss/spc.py:69); the entry scripts pass temperature only
+
 RNN_LIVE_PREFIXES = ("input_embed.", "rnn.", "rnn_fc.", "fc_seg.", "fc.", "fc_len.")
 
 
@@ -80,6 +82,7 @@ class _Shape:
             self.d_y = [f(N, H), f(N, H)]
             self.dg = f(N, 4 * H)
             self.d_x0, self.d_x, self.d_pre = f(N, H), f(N, H), f(N, H)
+            self.sc_ws, self.sc_loss = f(ops.supcon_ws_floats(N)), torch.zeros(1, dtype=torch.float32, device=dev)
 
 
 class RnnEngine:
@@ -97,6 +100,8 @@ class RnnEngine:
                                 live=lambda n: n.startswith(RNN_LIVE_PREFIXES))
         self.ws = ops.GemmWorkspace(self.device)
         self.erank_weight = 0.0
+        self.supcon_weight = 0.0            # --supcon_weight: total loss += weight * SupConLoss over the 'supcon' rows
+        self.supcon_temperature = 0.07      # --temperature
         self.defer_tail = False
         self.shapes = {}
         self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)     # (no dropout: kept for the surface)
@@ -168,8 +173,14 @@ class RnnEngine:
                     duration=w.actdur[:, K].view(B, POOL_ROWS), supcon=w.tgt.view(B, S, H))
 
     # ------------------------------------------------------------------------------------------------------
+    def _supcon_kw(self):
+        return dict(temperature=self.supcon_temperature, base_temperature=SUPCON_BASE_T, ignore_index=self.pad_idx,
+                    normalize=True)
+
     def losses(self, past_label, target, target_dur, with_grad=True, val_mode=False, tick=False):
-        """The 3 losses + counters of train_unimodal.py:188-225 (exclude index 120) in one launch; fills d_seg / d_actdur."""
+        """The 3 losses + counters of train_unimodal.py:188-225 (exclude index 120) in one launch; fills d_seg / d_actdur.
+        With supcon_weight > 0 (training only) the supervised contrastive loss of the L2-normalised 'supcon' rows over the
+        per-frame labels, padded frames ignored, follows: w.sc_loss holds it and loss[3] gains weight times it."""
         w, K = self.last["w"], self.K
         ops.losses_fwd_bwd_kseg(None if val_mode else w.seg, w.actdur[:, :K], w.actdur[:, K:], K + 1, past_label, target,
                                 target_dur, w.B, w.S, POOL_ROWS, K, self.Kseg, self.pad_idx, EXCLUDE_CLASS_IDX, w.loss,
@@ -177,12 +188,18 @@ class RnnEngine:
                                 d_seg=w.d_seg if with_grad else None, d_act=w.d_actdur[:, :K] if with_grad else None,
                                 d_dur=w.d_actdur[:, K:] if with_grad else None, ld_ddur=K + 1, ws=w.loss_ws,
                                 tick_a=self.step_t if tick else None)
+        if self.supcon_weight and with_grad and not val_mode:
+            lab = past_label.reshape(-1)
+            ops.supcon_fwd(w.tgt, lab, w.N, w.N, w.sc_ws, w.sc_loss, **self._supcon_kw())
+            w.loss[3:4].add_(w.sc_loss, alpha=self.supcon_weight)
+            self.last["supcon_labels"] = lab
         return w.loss, w.counts
 
     # ------------------------------------------------------------------------------------------------------
     def backward(self, d_seg=None, d_actdur=None, fused_adamw=None, adamw_next=False, d_supcon=None):
         """Adjoint of forward(); gradients land in the grad arena (written, not accumulated).  d_supcon (optional
-        [B,S,H]): a gradient on the 'supcon' output, added to rnn_fc's output gradient."""
+        [B,S,H]): a gradient on the 'supcon' output, added to rnn_fc's output gradient.  After losses() with supcon_weight
+        > 0 the contrastive term's gradient is added straight into it by its own kernel."""
         assert fused_adamw is None
         st = self.last
         w, a, H, ws = st["w"], self.arena, self.H, self.ws
@@ -201,6 +218,9 @@ class RnnEngine:
         ops.avgpool_rows_bwd(w.d_pooled, w.d_tgt, B, S, POOL_ROWS)
         if d_supcon is not None:
             ops.add_rowbcast(w.d_tgt, d_supcon.reshape(N, H).contiguous(), N, w.d_tgt)
+        if st.get("supcon_labels") is not None:
+            ops.supcon_bwd(w.tgt, st["supcon_labels"], N, N, w.sc_ws, w.d_tgt, gscale=self.supcon_weight, add=True,
+                           **self._supcon_kw())
         wgrad(w.d_tgt, w.y[1], a.g("rnn_fc.weight"), a.g("rnn_fc.bias"))
         ops.gemm(GEMM_NN, w.d_tgt, a.p("rnn_fc.weight"), w.d_y[1], ws=ws)
         # ---- the two LSTM layers, top down

@@ -1417,3 +1417,39 @@ def ce_rows_fwd_bwd(logits, target, pad_idx, loss_out, counts, d_logits=None):
     check(_lib.load().r3d_ce_rows_fwd_bwd(_p(logits), _ld(logits), _p(target), rows, Cc, pad_idx, _p(loss_out), _p(counts),
                                           _p(d_logits), _ld(d_logits) if d_logits is not None else 0, _stream()),
           "r3d_ce_rows_fwd_bwd")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# supervised contrastive loss (csrc/supcon.hip)
+# ----------------------------------------------------------------------------------------------------------
+def supcon_supported(D):
+    """supcon_fwd / supcon_bwd run rows of width D (host-only; the launches' own check)."""
+    return bool(_lib.load().r3d_supcon_supported(int(D)))
+
+
+def supcon_ws_floats(N):
+    return int(_lib.load().r3d_supcon_ws_floats(int(N)))
+
+
+def _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature, normalize):
+    N, D = x.shape
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == bsz
+    return (_p(_f32(x, "x")), _ld(x), _p(labels), bsz, N, A, D, 0 if ignore_index is None else 1,
+            0 if ignore_index is None else int(ignore_index), float(temperature), float(base_temperature), 1 if normalize else 0)
+
+
+def supcon_fwd(x, labels, bsz, A, ws, loss_out, *, temperature=0.07, base_temperature=0.07, ignore_index=None, normalize=False):
+    """x [N, D] (any row stride): the contrast rows, row r labelled labels[r % bsz] (None: r % bsz), the first A anchors.
+    Fills ws (supcon_ws_floats(N) floats: lse, positive mean, P, 1/|x|, anchor count) and loss_out[0]; enqueue only."""
+    head = _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature, normalize)
+    check(_lib.load().r3d_supcon_fwd(*head, _p(_f32(ws, "ws")), _p(_f32(loss_out, "loss_out")), _stream()), "r3d_supcon_fwd")
+
+
+def supcon_bwd(x, labels, bsz, A, ws, dx, *, d_loss=None, gscale=1.0, add=False, temperature=0.07, base_temperature=0.07,
+               ignore_index=None, normalize=False):
+    """dx [N, D] = (dx if add else 0) + gscale * d_loss[0] * d loss / d x from the forward's arguments and its ws; d_loss is
+    a device scalar (None: 1), so a graphed step needs no read-back."""
+    head = _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature, normalize)
+    check(_lib.load().r3d_supcon_bwd(*head, _p(_f32(ws, "ws")), _p(d_loss), float(gscale), _p(_f32(dx, "dx")), _ld(dx),
+                                     1 if add else 0, _stream()), "r3d_supcon_bwd")

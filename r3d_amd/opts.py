@@ -72,3 +72,19 @@ parser.add_argument("--erank_report", action="store_true", default=False,
                     help="after each validate() print the effective rank of the RGB embedding, the depth embedding and the "
                          "fused tokens over every unpadded frame of the validation set (a streaming QR fed by validate()'s "
                          "own forwards, no second pass; one GPU, SA-Fuser models)")
+parser.add_argument("--supcon_weight", type=float, default=0.0,
+                    help="RNN loop (train_unimodal) only: total loss += supcon_weight * SupConLoss(temperature=--temperature, "
+                         "normalize=True, ignore_index=pad_idx) over the B * S rows of the model's 'supcon' output with the "
+                         "per-frame labels (0 = the reference's loss and launches; the reference builds the criterion, "
+                         "main_nturgbd.py:137, and leaves its use commented out).  Build-defined: the rows are L2-normalised "
+                         "and padded frames skipped because unnormalised rnn_fc outputs are exactly the input on which the "
+                         "reference's SupConLoss returns nan, so the parity of this term is pinned only against the float64 "
+                         "restatement (tests/supcon_oracle.py).  The other loops refuse a non-zero value")
+
+
+def refuse_supcon_weight(args, loop):
+    """The loops whose models return no 'supcon' output call this first: a non-zero --supcon_weight is a ValueError."""
+    w = float(getattr(args, "supcon_weight", 0.0) or 0.0)
+    if w:
+        raise ValueError(f"supcon_weight {w}: {loop} drives a model without a 'supcon' output; the supervised contrastive "
+                         f"term is for the RNN loop (train_unimodal)")

@@ -18,6 +18,7 @@ import torch.distributed as dist
 from .model.futr_safuser_tokenfusion import FUTR
 from .model.futr_unsupervised_depth import FUTR as FUTRDepthQuery
 from .optim import FlatAdamW
+from .opts import refuse_supcon_weight
 from .parallel import DataParallelStep
 
 
@@ -349,6 +350,7 @@ def validate(model, val_loader, criterion, pad_idx, device):
 
 
 def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
+    refuse_supcon_weight(args, "train_proposed_depth")
     core = _unwrap(model)
     model.to(device)
     model.train()

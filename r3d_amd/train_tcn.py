@@ -21,6 +21,7 @@ import torch
 
 from .model.tcn import MustafaNet1DTCN
 from .optim import FlatAdamW
+from .opts import refuse_supcon_weight
 from .train_proposed_depth import _GraphedSteps
 
 
@@ -79,6 +80,7 @@ def validate(model, val_loader, pad_idx, device, model_save_path, epoch, best_ac
 
 
 def train(args, model, train_loader, val_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device):
+    refuse_supcon_weight(args, "train_tcn")
     core = _unwrap(model)
     model.to(device)
     model.train()

@@ -14,6 +14,12 @@ It is train_proposed_depth's loop except where the reference's differs (each can
 Kept from the shared loop: batches with fewer than 8 clips are skipped (:163), the epoch averages divide by (i + 1) (:234),
 validate() compares the normalised duration with the UNMASKED target and skips the seg loss (:86-113).  Multi-rank
 torch.distributed runs are refused (the reference's nn.DataParallel wrapper, main_nturgbd.py:131, is unwrapped).
+
+Build-defined addition: ``--supcon_weight W`` (default 0.0: none of the following is launched) adds W * SupConLoss(
+temperature=args.temperature, normalize=True, ignore_index=pad_idx) over the B * S rows of ``outputs['supcon']`` with the
+labels ``past_label.view(-1)`` -- the use main_nturgbd.py:137 prepares and the reference's loop leaves commented out --
+to the step's loss, inside the step (engine_rnn.RnnEngine.losses / backward); the epoch's ``Loss`` includes it and one
+``supcon loss`` line follows the ``seg loss`` line.  validate() is unchanged.
 """
 import os
 
@@ -44,7 +50,12 @@ def _to_dev(data, device):
 
 
 class _UnimodalSteps(_GraphedSteps):
-    """_GraphedSteps over the 4-tuple (features, past_label, trans_dur_future, trans_future_target): no depth buffer."""
+    """_GraphedSteps over the 4-tuple (features, past_label, trans_dur_future, trans_future_target): no depth buffer.
+    acc_sc: the epoch's sum of the supervised contrastive loss (--supcon_weight > 0), accumulated inside the step."""
+
+    def __init__(self, eng, acc_loss, acc_cnt, acc_sc=None):
+        super().__init__(eng, acc_loss, acc_cnt)
+        self.acc_sc = acc_sc
 
     def _enqueue(self, buf, lr, hyper, training):
         eng = self.eng
@@ -56,6 +67,8 @@ class _UnimodalSteps(_GraphedSteps):
         eng.adamw(lr, wd, betas=betas, eps=eps, ticked=True)
         self.acc_loss += loss
         self.acc_cnt += counts
+        if eng.supcon_weight and self.acc_sc is not None:
+            self.acc_sc += eng.last["w"].sc_loss
 
 
 def validate(model, val_loader, criterion, pad_idx, device):
@@ -100,6 +113,9 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     model.to(device)
     model.train()
     eng = core.engine()
+    # --supcon_weight: the supervised contrastive term on the 'supcon' output, part of every step (graphed or eager)
+    eng.supcon_weight = float(getattr(args, "supcon_weight", 0.0) or 0.0)
+    eng.supcon_temperature = float(getattr(args, "temperature", 0.07))
     min_batch = getattr(args, "min_batch", 8)
     print("Training Start")
     best_val_loss = float("inf")
@@ -107,10 +123,12 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     best_weight_acc = 0
     acc_loss = torch.zeros(4, dtype=torch.float64, device=eng.device)
     acc_cnt = torch.zeros(4, dtype=torch.int64, device=eng.device)
-    graphed = _UnimodalSteps(eng, acc_loss, acc_cnt) if getattr(args, "graph_steps", True) else None
+    acc_sc = torch.zeros(1, dtype=torch.float64, device=eng.device)
+    graphed = _UnimodalSteps(eng, acc_loss, acc_cnt, acc_sc) if getattr(args, "graph_steps", True) else None
     for epoch in range(args.epochs):
         acc_loss.zero_()
         acc_cnt.zero_()
+        acc_sc.zero_()
         i = -1
         for i, data in enumerate(train_loader):
             if data is None:
@@ -134,7 +152,10 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
                 optimizer.step()
             acc_loss += loss
             acc_cnt += counts
-        lsum, csum = acc_loss.cpu(), acc_cnt.cpu()                  # the single device->host read of the epoch
+            if eng.supcon_weight:
+                acc_sc += eng.last["w"].sc_loss
+        # the single device->host read of the epoch
+        lsum, csum = (torch.cat([acc_loss, acc_sc]) if eng.supcon_weight else acc_loss).cpu(), acc_cnt.cpu()
         denom = i + 1                                                # the reference divides by (i+1), skipped or not
         epoch_loss = float(lsum[3]) / denom if denom else 0.0
         print("Epoch [", (epoch + 1), "/", args.epochs, "] Loss : %.3f" % epoch_loss)
@@ -146,6 +167,8 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         if args.seg:
             acc_seg = int(csum[0]) / int(csum[1]) if int(csum[1]) else 0.0
             print("seg loss :%.3f" % (float(lsum[0]) / denom if denom else 0.0), ", seg acc : %.5f" % acc_seg)
+        if eng.supcon_weight:
+            print("supcon loss :%.3f" % (float(lsum[4]) / denom if denom else 0.0))
         scheduler.step()
         val_loss, val_acc, weight_acc = validate(model, val_loader, criterion, pad_idx, device)
         if val_acc > best_val_acc or weight_acc > best_weight_acc:
