@@ -436,8 +436,6 @@ __device__ __forceinline__ void fc3_fwd_fuser(const FcFwd& A, const int wg, floa
     const int f0 = (row0 >> 1) + 2 * q;
     const float pos0 = A.pos[(size_t)(f0 % A.S) * H + c], pos1 = A.pos[(size_t)((f0 + 1) % A.S) * H + c];
     const float bkv0 = A.bkv[wave * 16 + li], bkv1 = A.bkv[(wave + 8) * 16 + li];
-    const int cseg = (has12 ? wave : 0) * 16 + li;
-    const float bsg = A.bseg[cseg < A.K ? cseg : A.K - 1];
     __builtin_amdgcn_sched_barrier(0);
     bf3_stage_tile(imgH, kF3P1, 0, a_in, tid);
     __syncthreads();
@@ -509,6 +507,13 @@ __device__ __forceinline__ void fc3_fwd_fuser(const FcFwd& A, const int wg, floa
     __syncthreads();
     R3D_CHAIN_MARK(A.timeline, wg == 0, 4);
     // ---- stage 4: x3 = x1 (+ x0) + f1 . W2^T + b2 ; y = fuser.norm(x3) ; fused = mean over the token pair
+    // The segmentation head's bias is requested here, a stage ahead of its use, from a wave index the compiler cannot trace
+    // back to the prologue: requested there, the value and its column indices were spilled, and the spill of a LOADED value
+    // waits (vmcnt(0)) for everything requested in front of it -- the first three weight chunks.
+    int wseg = wave;
+    asm volatile("" : "+v"(wseg));
+    const int cseg = (wseg < nseg_t ? wseg : 0) * 16 + li;
+    const float bsg = A.bseg[cseg < A.K ? cseg : A.K - 1];
     acc0 = zero; acc1 = zero;
     bf3_chunk<4>(imgF, kF3P4, li, q, 0, b0, acc0, acc1);                               // c6
     __builtin_amdgcn_sched_barrier(0);
@@ -1019,8 +1024,8 @@ __device__ __forceinline__ void fc_bwd_query(const FcBwd& A, const int wgq, floa
 // y = x B^T product like the forward ones (no k-major staging); stages as fc_bwd_fuser
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void fc3_bwd_fuser(const FcBwd& A, const int wg, float* lds) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, q = lane >> 4;
+    int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int li = lane & 15, q = lane >> 4;
     unsigned short* img = reinterpret_cast<unsigned short*>(lds);
     unsigned short* imgH = img + kF3ImgH;
     unsigned short* imgV = img + kF3ImgV;
@@ -1029,8 +1034,8 @@ __device__ __forceinline__ void fc3_bwd_fuser(const FcBwd& A, const int wg, floa
     float* redB = redA + 2 * 8 * kFcRows;
     constexpr int H = kFcH;
     const int row0 = wg * kFcRows;
-    const int c = wave * 16 + li;
-    const int f0 = (row0 >> 1) + 2 * q;
+    int c = wave * 16 + li;
+    int f0 = (row0 >> 1) + 2 * q;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     R3D_CHAIN_MARK(A.timeline, wg == 0, 0);
     Bf3B b0, b1, b2;
@@ -1115,6 +1120,12 @@ __device__ __forceinline__ void fc3_bwd_fuser(const FcBwd& A, const int wg, floa
     }
     __syncthreads();
     R3D_CHAIN_MARK(A.timeline, wg == 0, 3);
+    // The thread's indices anew, opaque to the compiler: with the addresses of the later stages computed in the prologue
+    // and kept, stage 2 (three weight chunks, 16 values of u, the GELU derivative) ran out of registers, and what was
+    // spilled were weight chunks in flight -- each spill of a loaded value is a vmcnt(0) in the middle of stage 0.
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63; wave = tid >> 6; li = lane & 15; q = lane >> 4;
+    c = wave * 16 + li; f0 = (row0 >> 1) + 2 * q;
     // ---- stage 2: d_u = (d_x3 . W2) * GELU'(u)
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

@@ -241,11 +241,28 @@ __device__ __forceinline__ void losses_finalize8(const LossArgs& a, const float*
 
 constexpr int kTLHeads = 24;          // head outputs kept in registers / LDS per row (K + 1 <= 24)
 
+// Where the clip role below takes its operands from and what else it does with its two gradients.  This one is the role on
+// its own (tail_losses_kernel): everything from and to global memory.  The decoder chain (decoder_chain.hip) passes a policy
+// with kChip = true whose input rows, LayerNorm parameters and head weights wait in LDS and whose gradients also go to LDS for
+// the backward half of the same workgroup; the global stores are the same either way.
+struct TailGlobalIo {
+    static constexpr bool kChip = false;
+    __device__ __forceinline__ int tid() const { return threadIdx.x; }
+    __device__ __forceinline__ float x(int, int) const { return 0.f; }             // input row `wave` of the clip, column c
+    __device__ __forceinline__ float ln(int, int) const { return 0.f; }            // g3 | b3 | gF | bF (which, column)
+    __device__ __forceinline__ float wh(int, int) const { return 0.f; }            // head weight (head, column)
+    __device__ __forceinline__ float bh(int) const { return 0.f; }                 // head bias
+    __device__ __forceinline__ void grads(int, int, float, float) const {}         // (row, column, dx, dx2)
+    __device__ __forceinline__ void loads_requested() const {}                     // every global load of the role is issued
+};
+
 // The clip role of tail_losses_kernel (see losses.hip): workgroup of 8 waves, wave q = query row b*Q + q.  lg / dl: [8][kTLHeads + 8]
 // logits and their gradients, red: [8][4][128] LayerNorm parameter partials (workgroup-shared scratch).  Two workgroup barriers.
+template <class Io = TailGlobalIo>
 __device__ __forceinline__ void tail_clip_body(const r3d_tail_losses_args& t, const LossArgs& a, float* part, const int b,
-                                               float (*lg)[kTLHeads + 8], float (*dl)[kTLHeads + 8], float (*red)[4][128]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+                                               float (*lg)[kTLHeads + 8], float (*dl)[kTLHeads + 8], float (*red)[4][128],
+                                               const Io io = Io()) {
+    const int tid = io.tid(), lane = tid & 63, wave = tid >> 6;
     const int H = t.H, K = a.K, Q = a.Q, NH = t.n_head, N = a.B * a.S, BQ = a.B * a.Q;
     const int row = b * Q + wave;            // Q == 8 == waves (validated by the host)
     int cc[2];
@@ -254,20 +271,34 @@ __device__ __forceinline__ void tail_clip_body(const r3d_tail_losses_args& t, co
     for (int e = 0; e < 2; ++e) {
         const int c = lane + 64 * e;
         cc[e] = c < H ? c : H - 1;
-        x[e] = t.x[(size_t)row * H + cc[e]];
-        g3[e] = t.g3[cc[e]]; b3[e] = t.b3[cc[e]]; gF[e] = t.gF[cc[e]]; bF[e] = t.bF[cc[e]];
+        if (Io::kChip) {
+            x[e] = io.x(wave, cc[e]);
+            g3[e] = io.ln(0, cc[e]); b3[e] = io.ln(1, cc[e]); gF[e] = io.ln(2, cc[e]); bF[e] = io.ln(3, cc[e]);
+        } else {
+            x[e] = t.x[(size_t)row * H + cc[e]];
+            g3[e] = t.g3[cc[e]]; b3[e] = t.b3[cc[e]]; gF[e] = t.gF[cc[e]]; bF[e] = t.bF[cc[e]];
+        }
     }
     float wh[kTLHeads][2];
 #pragma unroll
     for (int k = 0; k < kTLHeads; ++k) {
         const int kc = k < NH ? k : NH - 1;
 #pragma unroll
-        for (int e = 0; e < 2; ++e) wh[k][e] = t.w_head[(size_t)kc * H + cc[e]];
+        for (int e = 0; e < 2; ++e) wh[k][e] = Io::kChip ? io.wh(kc, cc[e]) : t.w_head[(size_t)kc * H + cc[e]];
     }
     // backward operands that do not depend on anything computed here: issued now, consumed after the barrier
     float keep[2];
+    uint8_t keep_raw[2] = {0, 0};
+    if (Io::kChip) {
+        // (an UNCONDITIONAL load -- one under `t.drop ?` is waited for on the spot, and that wait would cover whatever
+        //  io.loads_requested() asks for: an absent mask reads a valid byte of g3 and is discarded)
+        const uint8_t* dp = t.drop ? t.drop + (size_t)row * H : reinterpret_cast<const uint8_t*>(t.g3);
 #pragma unroll
-    for (int e = 0; e < 2; ++e) keep[e] = t.drop ? t.drop_scale * (float)t.drop[(size_t)row * H + cc[e]] : 1.f;
+        for (int e = 0; e < 2; ++e) keep_raw[e] = dp[cc[e]];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) keep[e] = t.drop ? t.drop_scale * (float)t.drop[(size_t)row * H + cc[e]] : 1.f;
+    }
     // ... and the clip's labels, targets and durations (S <= 64, B*Q <= 64: one per lane -- validated by the host):
     // one round trip under the forward tail instead of four dependent ones after the barrier
     const bool small = a.S <= 64 && BQ <= 64;                    // (beyond that the label / mask scans loop, below)
@@ -276,7 +307,13 @@ __device__ __forceinline__ void tail_clip_body(const r3d_tail_losses_args& t, co
     const int64_t tgt_row = a.target[row];
     const float td_all = a.target_dur[lane < BQ ? lane : 0];
     const float td_clip = a.target_dur[(size_t)b * Q + (lane < Q ? lane : 0)];
-    const float dden_pre = a.dur_den ? *a.dur_den : 0.f;
+    const float* ddp = a.dur_den ? a.dur_den : t.g3;             // (kChip: unconditional as well)
+    const float dden_pre = Io::kChip ? *ddp : (a.dur_den ? *a.dur_den : 0.f);
+    io.loads_requested();
+    if (Io::kChip) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) keep[e] = t.drop ? t.drop_scale * (float)keep_raw[e] : 1.f;
+    }
     // ---- forward tail: norm3 -> decoder.norm -> heads
     float y3[2], yF[2], m3, r3, mF, rF;
     ln2_apply(x, g3, b3, H, lane, y3, m3, r3);
@@ -295,7 +332,7 @@ __device__ __forceinline__ void tail_clip_body(const r3d_tail_losses_args& t, co
 #pragma unroll
         for (int k = 0; k < kTLHeads; ++k) {
             if (k < NH) {                                     // wave-uniform
-                const float v = wave_sum(p[k]) + t.b_head[k];
+                const float v = wave_sum(p[k]) + (Io::kChip ? io.bh(k) : t.b_head[k]);
                 if (lane == 0) { t.out[(size_t)row * t.ld_out + k] = v; lg[wave][k] = v; }
             }
         }
@@ -414,6 +451,7 @@ __device__ __forceinline__ void tail_clip_body(const r3d_tail_losses_args& t, co
             const float o = r3 * (gg[e] - u1 - xh[e] * u2);
             t.dx[(size_t)row * H + c] = o;
             t.dx2[(size_t)row * H + c] = o * keep[e];
+            io.grads(wave, c, o, o * keep[e]);
             red[wave][0][c] = agF[e]; red[wave][1][c] = abF[e]; red[wave][2][c] = ag3[e]; red[wave][3][c] = ab3[e];
         }
     }

@@ -29,11 +29,22 @@ template <bool WG> __device__ __forceinline__ void mha_unit_sync() {
     else __builtin_amdgcn_wave_barrier();
 }
 
-template <int DH, int LQ, bool WG>
-__device__ __forceinline__ void mha_fwd_small_unit(const MhaArgs& a, const int unit, float* lds) {
-    float* qs = lds;                              // [LQ][DH], 16-byte aligned
-    float* sc = lds + LQ * DH;                    // [LQ][64]
-    float* vc = sc + LQ * 64;                     // [64][DH + 1]
+// The unit in two halves, so that a caller can REQUEST the unit's operands, request other loads behind them (loads return in
+// issue order: whatever is requested first is waited for alone) and only then compute: *_load issues every global load of
+// the unit into a register struct and waits for nothing, *_compute stages them in LDS and does the arithmetic.
+template <int DH, int LQ> struct MhaFwdRegs {
+    float4 k4[DH / 4], v4[DH / 4];
+    float qv[(LQ * DH + 63) / 64];
+    uint8_t kraw[LQ];
+    uint8_t kpm_raw;
+    int64_t lab_raw;
+};
+
+// what else the unit does with an output value (row i of the clip, column of the hidden vector): nothing
+struct MhaNoSink { __device__ __forceinline__ void operator()(int, int, float) const {} };
+
+template <int DH, int LQ>
+__device__ __forceinline__ void mha_fwd_small_load(const MhaArgs& a, const int unit, MhaFwdRegs<DH, LQ>& R) {
     const int b = unit / a.heads, h = unit % a.heads;
     const int lane = threadIdx.x & 63, Lk = a.Lk;
     const int jc = lane < Lk ? lane : Lk - 1;
@@ -41,29 +52,43 @@ __device__ __forceinline__ void mha_fwd_small_unit(const MhaArgs& a, const int u
     const float4* kr = reinterpret_cast<const float4*>(a.k + ((size_t)b * Lk + jc) * a.ldk + h * DH);
     const float4* vr = reinterpret_cast<const float4*>(a.v + ((size_t)b * Lk + jc) * a.ldv + h * DH);
     const size_t pbase = ((size_t)(b * a.heads + h) * LQ) * Lk;
-    float4 k4[DH / 4], v4[DH / 4];
 #pragma unroll
-    for (int t = 0; t < DH / 4; ++t) { k4[t] = kr[t]; v4[t] = vr[t]; }
-    float qv[(LQ * DH + 63) / 64];
+    for (int t = 0; t < DH / 4; ++t) { R.k4[t] = kr[t]; R.v4[t] = vr[t]; }
 #pragma unroll
     for (int t = 0; t < (LQ * DH + 63) / 64; ++t) {
         const int e = lane + 64 * t, ec = e < LQ * DH ? e : LQ * DH - 1;
-        qv[t] = qb[(size_t)(ec / DH) * a.ldq + (ec % DH)];
+        R.qv[t] = qb[(size_t)(ec / DH) * a.ldq + (ec % DH)];
     }
     // optional operands as UNCONDITIONAL loads (a load under a branch is waited for on the spot): an absent one reads a
     // valid address (the key row) and is discarded; the raw values are converted only after the staging barrier
     const bool has_drop = a.drop != nullptr, has_kpm = a.kpm != nullptr, has_lab = a.key_label != nullptr;
     const uint8_t* dp = has_drop ? a.drop + pbase + jc : reinterpret_cast<const uint8_t*>(kr);
     const size_t dst_ = has_drop ? (size_t)Lk : 0;
-    uint8_t kraw[LQ];
 #pragma unroll
-    for (int i = 0; i < LQ; ++i) kraw[i] = dp[(size_t)i * dst_];
-    const uint8_t kpm_raw = *(has_kpm ? a.kpm + (size_t)b * Lk + jc : reinterpret_cast<const uint8_t*>(kr));
-    const int64_t lab_raw = *(has_lab ? a.key_label + (size_t)b * Lk + jc : reinterpret_cast<const int64_t*>(kr));
+    for (int i = 0; i < LQ; ++i) R.kraw[i] = dp[(size_t)i * dst_];
+    R.kpm_raw = *(has_kpm ? a.kpm + (size_t)b * Lk + jc : reinterpret_cast<const uint8_t*>(kr));
+    R.lab_raw = *(has_lab ? a.key_label + (size_t)b * Lk + jc : reinterpret_cast<const int64_t*>(kr));
+}
+
+template <int DH, int LQ, bool WG, class Sink = MhaNoSink>
+__device__ __forceinline__ void mha_fwd_small_compute(const MhaArgs& a, const int unit, float* lds, const MhaFwdRegs<DH, LQ>& R,
+                                                      const Sink sink = Sink()) {
+    float* qs = lds;                              // [LQ][DH], 16-byte aligned
+    float* sc = lds + LQ * DH;                    // [LQ][64]
+    float* vc = sc + LQ * 64;                     // [64][DH + 1]
+    const int b = unit / a.heads, h = unit % a.heads;
+    const int lane = threadIdx.x & 63, Lk = a.Lk;
+    const size_t pbase = ((size_t)(b * a.heads + h) * LQ) * Lk;
+    const bool has_drop = a.drop != nullptr, has_kpm = a.kpm != nullptr, has_lab = a.key_label != nullptr;
+    const float4 (&k4)[DH / 4] = R.k4;
+    const float4 (&v4)[DH / 4] = R.v4;
+    const uint8_t (&kraw)[LQ] = R.kraw;
+    const uint8_t kpm_raw = R.kpm_raw;
+    const int64_t lab_raw = R.lab_raw;
 #pragma unroll
     for (int t = 0; t < (LQ * DH + 63) / 64; ++t) {
         const int e = lane + 64 * t;
-        if (e < LQ * DH) qs[e] = qv[t];
+        if (e < LQ * DH) qs[e] = R.qv[t];
     }
 #pragma unroll
     for (int t = 0; t < DH / 4; ++t) {
@@ -101,50 +126,80 @@ __device__ __forceinline__ void mha_fwd_small_unit(const MhaArgs& a, const int u
             float s = 0.f;
             for (int r = 0; r < Lk; ++r) s += sc[i * 64 + r] * vc[r * (DH + 1) + d];
             a.o[((size_t)b * LQ + i) * a.ldo + h * DH + d] = s;
+            sink(i, h * DH + d, s);
         }
     }
 }
 
+template <int DH, int LQ, bool WG>
+__device__ __forceinline__ void mha_fwd_small_unit(const MhaArgs& a, const int unit, float* lds) {
+    MhaFwdRegs<DH, LQ> R;
+    mha_fwd_small_load<DH, LQ>(a, unit, R);
+    mha_fwd_small_compute<DH, LQ, WG>(a, unit, lds, R);
+}
+
 constexpr int mha_small_bwd_lds_floats(int DH, int LQ) { return 2 * LQ * DH + LQ * 64 + 64 * (DH + 1); }
 
-template <int DH, int LQ, bool WG>
-__device__ __forceinline__ void mha_bwd_small_unit(const MhaArgs& a, const int unit, float* lds) {
+// The backward unit's operands in two groups: what the forward left (K, V, Q, the probabilities, the keep mask) can be
+// requested long before the output gradient exists; d_o comes from global memory (DoLds = false: requested in *_load too) or
+// from a [LQ][ld_tile] fp32 LDS tile of the clip's rows that the caller filled behind a barrier (DoLds = true).
+template <int DH, int LQ> struct MhaBwdRegs {
+    float4 k4[DH / 4], v4[DH / 4];
+    float qv[(LQ * DH + 63) / 64], dv_[(LQ * DH + 63) / 64];
+    float P[LQ];
+    uint8_t kraw[LQ];
+};
+
+template <int DH, int LQ, bool DoLds>
+__device__ __forceinline__ void mha_bwd_small_load(const MhaArgs& a, const int unit, MhaBwdRegs<DH, LQ>& R,
+                                                   const int lane = threadIdx.x & 63) {
+    const int b = unit / a.heads, h = unit % a.heads;
+    const int Lk = a.Lk;
+    const int jc = lane < Lk ? lane : Lk - 1;
+    const float* qb = a.q + (size_t)b * LQ * a.ldq + h * DH;
+    const float4* kr = reinterpret_cast<const float4*>(a.k + ((size_t)b * Lk + jc) * a.ldk + h * DH);
+    const float4* vr = reinterpret_cast<const float4*>(a.v + ((size_t)b * Lk + jc) * a.ldv + h * DH);
+    const size_t pbase = ((size_t)(b * a.heads + h) * LQ) * Lk;
+#pragma unroll
+    for (int t = 0; t < DH / 4; ++t) { R.k4[t] = kr[t]; R.v4[t] = vr[t]; }
+#pragma unroll
+    for (int t = 0; t < (LQ * DH + 63) / 64; ++t) {
+        const int e = lane + 64 * t, ec = e < LQ * DH ? e : LQ * DH - 1;
+        R.qv[t] = qb[(size_t)(ec / DH) * a.ldq + (ec % DH)];
+        if (!DoLds) R.dv_[t] = (a.d_o + (size_t)b * LQ * a.lddo + h * DH)[(size_t)(ec / DH) * a.lddo + (ec % DH)];
+    }
+    const bool has_drop = a.drop != nullptr;
+    const uint8_t* dp = has_drop ? a.drop + pbase + jc : reinterpret_cast<const uint8_t*>(kr);
+    const size_t dst_ = has_drop ? (size_t)Lk : 0;
+#pragma unroll
+    for (int i = 0; i < LQ; ++i) {
+        R.P[i] = a.probs[pbase + (size_t)i * Lk + jc];
+        R.kraw[i] = dp[(size_t)i * dst_];
+    }
+}
+
+template <int DH, int LQ, bool WG, bool DoLds>
+__device__ __forceinline__ void mha_bwd_small_compute(const MhaArgs& a, const int unit, float* lds, const MhaBwdRegs<DH, LQ>& R,
+                                                      const float* do_tile = nullptr, const int ld_tile = 0,
+                                                      const int lane = threadIdx.x & 63) {
     float* qs = lds;                              // [LQ][DH], 16-byte aligned
     float* dos = lds + LQ * DH;                   // [LQ][DH], 16-byte aligned
     float* ds = dos + LQ * DH;                    // [LQ][64]
     float* kc = ds + LQ * 64;                     // [64][DH + 1]
     const int b = unit / a.heads, h = unit % a.heads;
-    const int lane = threadIdx.x & 63, Lk = a.Lk;
-    const int jc = lane < Lk ? lane : Lk - 1;
-    const float* qb = a.q + (size_t)b * LQ * a.ldq + h * DH;
-    const float* dob = a.d_o + (size_t)b * LQ * a.lddo + h * DH;
-    const float4* kr = reinterpret_cast<const float4*>(a.k + ((size_t)b * Lk + jc) * a.ldk + h * DH);
-    const float4* vr = reinterpret_cast<const float4*>(a.v + ((size_t)b * Lk + jc) * a.ldv + h * DH);
-    const size_t pbase = ((size_t)(b * a.heads + h) * LQ) * Lk;
-    float4 k4[DH / 4], v4[DH / 4];
-#pragma unroll
-    for (int t = 0; t < DH / 4; ++t) { k4[t] = kr[t]; v4[t] = vr[t]; }
-    float qv[(LQ * DH + 63) / 64], dv_[(LQ * DH + 63) / 64];
-#pragma unroll
-    for (int t = 0; t < (LQ * DH + 63) / 64; ++t) {
-        const int e = lane + 64 * t, ec = e < LQ * DH ? e : LQ * DH - 1;
-        qv[t] = qb[(size_t)(ec / DH) * a.ldq + (ec % DH)];
-        dv_[t] = dob[(size_t)(ec / DH) * a.lddo + (ec % DH)];
-    }
+    const int Lk = a.Lk;
     const bool has_drop = a.drop != nullptr;
-    const uint8_t* dp = has_drop ? a.drop + pbase + jc : reinterpret_cast<const uint8_t*>(kr);
-    const size_t dst_ = has_drop ? (size_t)Lk : 0;
-    float P[LQ];
-    uint8_t kraw[LQ];
-#pragma unroll
-    for (int i = 0; i < LQ; ++i) {
-        P[i] = a.probs[pbase + (size_t)i * Lk + jc];
-        kraw[i] = dp[(size_t)i * dst_];
-    }
+    const float4 (&k4)[DH / 4] = R.k4;
+    const float4 (&v4)[DH / 4] = R.v4;
+    const float (&P)[LQ] = R.P;
+    const uint8_t (&kraw)[LQ] = R.kraw;
 #pragma unroll
     for (int t = 0; t < (LQ * DH + 63) / 64; ++t) {
         const int e = lane + 64 * t;
-        if (e < LQ * DH) { qs[e] = qv[t]; dos[e] = dv_[t]; }
+        if (e < LQ * DH) {
+            qs[e] = R.qv[t];
+            dos[e] = DoLds ? do_tile[(e / DH) * ld_tile + h * DH + (e % DH)] : R.dv_[t];
+        }
     }
 #pragma unroll
     for (int t = 0; t < DH / 4; ++t) {
@@ -203,6 +258,13 @@ __device__ __forceinline__ void mha_bwd_small_unit(const MhaArgs& a, const int u
             dvr[t] = gv;
         }
     }
+}
+
+template <int DH, int LQ, bool WG>
+__device__ __forceinline__ void mha_bwd_small_unit(const MhaArgs& a, const int unit, float* lds) {
+    MhaBwdRegs<DH, LQ> R;
+    mha_bwd_small_load<DH, LQ, false>(a, unit, R);
+    mha_bwd_small_compute<DH, LQ, WG, false>(a, unit, lds, R);
 }
 
 }  // namespace r3d
