@@ -833,6 +833,54 @@ int r3d_supcon_bwd(const float* x, int ldx, const int64_t* labels, int bsz, int 
                    int64_t ignore_index, float temperature, float base_temperature, int normalize, const float* ws,
                    const float* d_loss, float gscale, float* dx, int lddx, int add, void* stream);
 
+/* ---- temporal auxiliary losses (temporal.hip; reference utils.py :229-321, :493; train_unsupervised.py :34) --------------
+ * Every call enqueues only; no allocation, no atomics, fixed-order reductions (the same call gives the same bits), no host
+ * synchronisation.  B >= 1 clips of T >= 1 frames, B T < 2^30, B <= 65535; rows are x [B T, W] with row stride ldx >= W.
+ * r3d_label_runs: labels int64 [B, T].  A run starts at t = 0 and wherever labels[b, t] != labels[b, t - 1].  Writes, all
+ *   int32: first / last [B, T] (the first and last frame of the frame's run), starts [B, T] (starts[b, r] = first frame of
+ *   run r, T past the last run), count [B].  One launch.
+ * r3d_temporal_width_supported: 1 <= W <= 256, the width limit of both losses below (host-only).
+ *
+ * Cluster loss, x [B T, C]: run r of clip b has n_r frames and mean m_r, R_b = count[b], total = sum_b R_b,
+ *   loss = sum_{b,r} (1 / (n_r C)) sum_{t in r, c} (x - m_r)^2 / total
+ *        + sum_{b: R_b > 1} sum_{i<j} 1 / (1e-5 + |m_i - m_j|) / (M (n_last - 1)),
+ *   M = clips with R_b > 1, n_last = R_b of the last of them in batch order (0 when M = 0).  The backward takes the
+ *   gradient of |m_i - m_j| as 0 where it is 0.  T <= 32 * 65535.
+ * ws: r3d_tcluster_ws_floats(B, T, C) floats: the run means, the runs' intra terms, the pair-tile partials, 1 / total and
+ *   1 / (M (n_last - 1)); the forward writes it, the backward reads it.
+ * r3d_tcluster_bwd: dx (row stride lddx >= C) = (add != 0 ? dx : 0) + gscale * d_loss[0] * d loss / d x; d_loss a device
+ *   scalar (NULL: 1).
+ *
+ * Contrastive loss, x [B T, D]: z = x / max(|x|, 1e-12), s = z z^T / temperature per clip, p_tc = softmax over all c of the
+ *   clip.  Frame t of the run (st, en): P(t) = { c : st <= c <= en, c != t - st }, |P_r| = sum_{t in r} |P(t)|,
+ *   loss = sum_b sum_r sum_{t in r} sum_{c in P(t)} -log(p_tc + 1e-5) / (|P_r| + 1e-5) / B.
+ * 64 x 64 score tiles streamed through LDS, no [T, T] tensor.  ws: r3d_tcontrast_ws_floats(B, T) = 5 B T floats: lse, Q_t =
+ *   sum_{P(t)} p / (p + 1e-5), 1 / max(|x|, 1e-12), the row's loss term and max(|x|, 1e-12).  r3d_tcontrast_bwd: dx as above, one launch.
+ *
+ * Focal loss, pred [N, C] (row stride ld >= C, any C >= 1), gold int64 [N].  A row is masked when gold equals pad_idx,
+ *   or exclude_idx with has_exclude != 0, or lies outside [0, C).  With CE = lse - pred[gold], p = exp(-CE):
+ *   loss = sum over unmasked rows of alpha (1 - p)^gamma CE + penalty_weight [argmax == pad_idx], divided by N.  gamma >= 1.
+ * r3d_focal_rows: loss_out != NULL: loss_out[0] = loss, flags uint8 [N] = [unmasked and argmax == gold], counts int64 [2] =
+ *   (sum of flags, unmasked rows), ws [N] floats of scratch.  d_pred != NULL: d_pred (row stride lddp >= C) = (add != 0 ?
+ *   d_pred : 0) + gscale * d_loss[0] * d loss / d pred.  At least one of loss_out and d_pred.
+ * A refused shape returns R3D_EINVAL before anything is enqueued. */
+int r3d_label_runs(const int64_t* labels, int B, int T, int* first, int* last, int* starts, int* count, void* stream);
+int r3d_temporal_width_supported(int W);
+int64_t r3d_tcluster_ws_floats(int B, int T, int C);
+int r3d_tcluster_fwd(const float* x, int ldx, int B, int T, int C, const int* starts, const int* last, const int* count,
+                     float* ws, float* loss_out, void* stream);
+int r3d_tcluster_bwd(const float* x, int ldx, int B, int T, int C, const int* starts, const int* last, const int* count,
+                     const float* ws, const float* d_loss, float gscale, float* dx, int lddx, int add, void* stream);
+int64_t r3d_tcontrast_ws_floats(int B, int T);
+int r3d_tcontrast_fwd(const float* x, int ldx, int B, int T, int D, const int* first, const int* last, float temperature,
+                      float* ws, float* loss_out, void* stream);
+int r3d_tcontrast_bwd(const float* x, int ldx, int B, int T, int D, const int* first, const int* last, float temperature,
+                      const float* ws, const float* d_loss, float gscale, float* dx, int lddx, int add, void* stream);
+int r3d_focal_rows(const float* pred, int ld, const int64_t* gold, int N, int C, int64_t pad_idx, int has_exclude,
+                   int64_t exclude_idx, float alpha, float gamma, float penalty_weight, float* ws, float* loss_out,
+                   uint8_t* flags, int64_t* counts, const float* d_loss, float gscale, float* d_pred, int lddp, int add,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -298,6 +298,15 @@ _SIGNATURES = {
     "r3d_supcon_ws_floats": ([_I], C.c_int64),
     "r3d_supcon_fwd": ([_P, _I, _P, _I, _I, _I, _I, _I, _L, _F, _F, _I, _P, _P, _P], C.c_int),
     "r3d_supcon_bwd": ([_P, _I, _P, _I, _I, _I, _I, _I, _L, _F, _F, _I, _P, _P, _F, _P, _I, _I, _P], C.c_int),
+    "r3d_label_runs": ([_P, _I, _I, _P, _P, _P, _P, _P], C.c_int),
+    "r3d_temporal_width_supported": ([_I], C.c_int),
+    "r3d_tcluster_ws_floats": ([_I, _I, _I], C.c_int64),
+    "r3d_tcluster_fwd": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], C.c_int),
+    "r3d_tcluster_bwd": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P], C.c_int),
+    "r3d_tcontrast_ws_floats": ([_I, _I], C.c_int64),
+    "r3d_tcontrast_fwd": ([_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P], C.c_int),
+    "r3d_tcontrast_bwd": ([_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _F, _P, _I, _I, _P], C.c_int),
+    "r3d_focal_rows": ([_P, _I, _P, _I, _I, _L, _I, _L, _F, _F, _F, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P], C.c_int),
 }
 
 EXPORTS = tuple(_SIGNATURES)

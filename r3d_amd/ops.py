@@ -1453,3 +1453,90 @@ def supcon_bwd(x, labels, bsz, A, ws, dx, *, d_loss=None, gscale=1.0, add=False,
     head = _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature, normalize)
     check(_lib.load().r3d_supcon_bwd(*head, _p(_f32(ws, "ws")), _p(d_loss), float(gscale), _p(_f32(dx, "dx")), _ld(dx),
                                      1 if add else 0, _stream()), "r3d_supcon_bwd")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# temporal auxiliary losses (csrc/temporal.hip)
+# ----------------------------------------------------------------------------------------------------------
+def _i32(t, name, n):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == n, f"{name}: int32 device tensor of {n}"
+    return t
+
+
+def label_runs(labels, first, last, starts, count):
+    """labels int64 [B, T] -> first / last / starts int32 [B, T], count int32 [B] (see r3d_label_runs); one launch."""
+    B, T = labels.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    check(_lib.load().r3d_label_runs(_p(labels), B, T, _p(_i32(first, "first", B * T)), _p(_i32(last, "last", B * T)),
+                                     _p(_i32(starts, "starts", B * T)), _p(_i32(count, "count", B)), _stream()), "r3d_label_runs")
+
+
+def temporal_width_supported(W):
+    """The cluster and contrastive kernels run rows of width W (host-only; the launches' own check)."""
+    return bool(_lib.load().r3d_temporal_width_supported(int(W)))
+
+
+def tcluster_ws_floats(B, T, C):
+    return int(_lib.load().r3d_tcluster_ws_floats(int(B), int(T), int(C)))
+
+
+def tcontrast_ws_floats(B, T):
+    return int(_lib.load().r3d_tcontrast_ws_floats(int(B), int(T)))
+
+
+def _rows_bt(x, B, T, name):
+    """x [B * T, W] with unit column stride: (pointer, row stride, W)"""
+    assert x.shape[0] == B * T, f"{name} has {x.shape[0]} rows, expected {B * T}"
+    return _p(_f32(x, name)), _ld(x), x.shape[1]
+
+
+def tcluster_fwd(x, B, T, starts, last, count, ws, loss_out):
+    """x [B * T, C] (any row stride): fills ws (tcluster_ws_floats(B, T, C) floats) and loss_out[0]; enqueue only."""
+    px, ld, Cw = _rows_bt(x, B, T, "x")
+    check(_lib.load().r3d_tcluster_fwd(px, ld, B, T, Cw, _p(_i32(starts, "starts", B * T)), _p(_i32(last, "last", B * T)),
+                                       _p(_i32(count, "count", B)), _p(_f32(ws, "ws")), _p(_f32(loss_out, "loss_out")),
+                                       _stream()), "r3d_tcluster_fwd")
+
+
+def tcluster_bwd(x, B, T, starts, last, count, ws, dx, *, d_loss=None, gscale=1.0, add=False):
+    """dx [B * T, C] = (dx if add else 0) + gscale * d_loss[0] * d loss / d x from the forward's ws; d_loss a device scalar."""
+    px, ld, Cw = _rows_bt(x, B, T, "x")
+    pdx, lddx, Cd = _rows_bt(dx, B, T, "dx")
+    assert Cd == Cw
+    check(_lib.load().r3d_tcluster_bwd(px, ld, B, T, Cw, _p(_i32(starts, "starts", B * T)), _p(_i32(last, "last", B * T)),
+                                       _p(_i32(count, "count", B)), _p(_f32(ws, "ws")), _p(d_loss), float(gscale), pdx, lddx,
+                                       1 if add else 0, _stream()), "r3d_tcluster_bwd")
+
+
+def tcontrast_fwd(x, B, T, first, last, ws, loss_out, *, temperature=0.07):
+    """x [B * T, D] (any row stride): fills ws (5 B T floats: lse, Q, 1/|x|, row terms, |x|) and loss_out[0]; enqueue only."""
+    px, ld, D = _rows_bt(x, B, T, "x")
+    check(_lib.load().r3d_tcontrast_fwd(px, ld, B, T, D, _p(_i32(first, "first", B * T)), _p(_i32(last, "last", B * T)),
+                                        float(temperature), _p(_f32(ws, "ws")), _p(_f32(loss_out, "loss_out")), _stream()),
+          "r3d_tcontrast_fwd")
+
+
+def tcontrast_bwd(x, B, T, first, last, ws, dx, *, temperature=0.07, d_loss=None, gscale=1.0, add=False):
+    px, ld, D = _rows_bt(x, B, T, "x")
+    pdx, lddx, Dd = _rows_bt(dx, B, T, "dx")
+    assert Dd == D
+    check(_lib.load().r3d_tcontrast_bwd(px, ld, B, T, D, _p(_i32(first, "first", B * T)), _p(_i32(last, "last", B * T)),
+                                        float(temperature), _p(_f32(ws, "ws")), _p(d_loss), float(gscale), pdx, lddx,
+                                        1 if add else 0, _stream()), "r3d_tcontrast_bwd")
+
+
+def focal_rows(pred, gold, pad_idx, *, exclude_idx=None, alpha=1.0, gamma=2.0, penalty_weight=0.0, ws=None, loss_out=None,
+               flags=None, counts=None, d_pred=None, d_loss=None, gscale=1.0, add=False):
+    """The focal loss over the rows of pred [N, C] (any row stride).  With loss_out: loss_out[0], flags (bool / uint8 [N]),
+    counts (int64 [2]: correct, unmasked) and the scratch ws [N] are written.  With d_pred: d_pred = (d_pred if add else 0) +
+    gscale * d_loss[0] * d loss / d pred in the same launch."""
+    N, Cc = pred.shape
+    assert gold.dtype == torch.int64 and gold.is_contiguous() and gold.numel() == N
+    if loss_out is not None:
+        assert ws.numel() >= N and flags.numel() == N and flags.element_size() == 1 and flags.is_contiguous()
+        assert counts.dtype == torch.int64 and counts.numel() == 2
+    check(_lib.load().r3d_focal_rows(_p(_f32(pred, "pred")), _ld(pred), _p(gold), N, Cc, int(pad_idx),
+                                     0 if exclude_idx is None else 1, 0 if exclude_idx is None else int(exclude_idx),
+                                     float(alpha), float(gamma), float(penalty_weight), _p(ws), _p(loss_out), _p(flags),
+                                     _p(counts), _p(d_loss), float(gscale), _p(d_pred), _ld(d_pred) if d_pred is not None else 0,
+                                     1 if add else 0, _stream()), "r3d_focal_rows")
