@@ -13,6 +13,18 @@
 
 namespace r3d {
 
+// One element of the update (pp, gg, mm, vv: float4 locals; c: x / y / z / w).  Every kernel that uses it does so under
+// `#pragma clang fp contract(off)` (see adamw_body): the bits of an update must not depend on the launch that makes it.
+#define R3D_ADAM1(c)                                               \
+        {                                                          \
+            const float gr = gg.c * gscale;                        \
+            pp.c *= decay;                                         \
+            mm.c = mm.c + (gr - mm.c) * omb1;                      \
+            vv.c = vv.c * b2 + gr * gr * omb2;                     \
+            const float den = sqrtf(vv.c) / bc2_sqrt + eps;        \
+            pp.c -= step_size * (mm.c / den);                      \
+        }
+
 __device__ __forceinline__ void adamw_body(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
                                            float4* __restrict__ v, size_t n4, const float* lr_ptr, const int64_t* step_ptr,
                                            float b1, float b2, float eps, float wd, float gscale, unsigned bid, unsigned nb) {
@@ -28,15 +40,6 @@ __device__ __forceinline__ void adamw_body(float4* __restrict__ p, const float4*
     const float decay = 1.0f - lr * wd;
     const float step_size = lr / bc1;
     const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
-#define R3D_ADAM1(c)                                               \
-        {                                                          \
-            const float gr = gg.c * gscale;                        \
-            pp.c *= decay;                                         \
-            mm.c = mm.c + (gr - mm.c) * omb1;                      \
-            vv.c = vv.c * b2 + gr * gr * omb2;                     \
-            const float den = sqrtf(vv.c) / bc2_sqrt + eps;        \
-            pp.c -= step_size * (mm.c / den);                      \
-        }
     // two grid-strides per iteration: eight 16-byte loads in flight per lane before the first use (arenas beyond the
     // 256 MiB Infinity Cache are a pure HBM stream: more bytes in flight per CU, measured at the cfg4 / cfg5 arena sizes;
     // consecutive 4 KB pieces per workgroup instead of grid strides measured 10 % slower there)
@@ -57,7 +60,6 @@ __device__ __forceinline__ void adamw_body(float4* __restrict__ p, const float4*
         R3D_ADAM1(x) R3D_ADAM1(y) R3D_ADAM1(z) R3D_ADAM1(w)
         p[i] = pp; m[i] = mm; v[i] = vv;
     }
-#undef R3D_ADAM1
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(float4* __restrict__ p, const float4* __restrict__ g,
@@ -73,6 +75,9 @@ __global__ __launch_bounds__(256) void adamw_2d_kernel(float* __restrict__ p, co
                                                        float* __restrict__ m, float* __restrict__ v, int rows, int cols4,
                                                        int ld4, const float* lr_ptr, const int64_t* step_ptr, float b1,
                                                        float b2, float eps, float wd, float gscale) {
+    // as adamw_body: without this the shard's elements were fused differently from the flat launch's, and a parameter's update
+    // differed in its last bit between the tensor-parallel and the single-device run
+#pragma clang fp contract(off)
     const float lr = *lr_ptr;
     const double step = (double)*step_ptr;
     const float bc1 = (float)(1.0 - pow((double)b1, step));
@@ -85,22 +90,13 @@ __global__ __launch_bounds__(256) void adamw_2d_kernel(float* __restrict__ p, co
         const size_t i = (e / cols4) * ld4 + (e % cols4);
         float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-#define R3D_ADAM2(c)                                               \
-        {                                                          \
-            const float gr = gg.c * gscale;                        \
-            pp.c *= decay;                                         \
-            mm.c = mm.c + (gr - mm.c) * omb1;                      \
-            vv.c = vv.c * b2 + gr * gr * omb2;                     \
-            const float den = sqrtf(vv.c) / bc2_sqrt + eps;        \
-            pp.c -= step_size * (mm.c / den);                      \
-        }
-        R3D_ADAM2(x) R3D_ADAM2(y) R3D_ADAM2(z) R3D_ADAM2(w)
-#undef R3D_ADAM2
+        R3D_ADAM1(x) R3D_ADAM1(y) R3D_ADAM1(z) R3D_ADAM1(w)
         reinterpret_cast<float4*>(p)[i] = pp;
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
     }
 }
+#undef R3D_ADAM1
 
 __device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
 
