@@ -881,6 +881,38 @@ int r3d_focal_rows(const float* pred, int ld, const int64_t* gold, int N, int C,
                    uint8_t* flags, int64_t* counts, const float* d_loss, float gscale, float* d_pred, int lddp, int add,
                    void* stream);
 
+/* ---- AFFT baseline: the pooled-head chain (csrc/afft.hip; model/afft.py:189-201 of the reference) ----------------
+ * Behind the fused tokens [B S, H] the model is pooled = adaptive_avg_pool1d(fused, Q) (window of output q:
+ * [floor(q S / Q), ceil((q + 1) S / Q)), padded frames included) and actdur = pooled . w_head^T + b_head with w_head =
+ * [fc.weight ; fc_len.weight] [K + 1, H].  One workgroup per clip.
+ * r3d_afft_head_fwd: writes pooled [B Q, H] (contiguous) and out [B Q, K + 1] (row stride ld_out); reads the fields up to
+ *   ld_out, B, S, Q, K, H only.
+ * r3d_afft_head_step: the same, then the clip's anticipation CE rows and duration unit exactly as r3d_losses_fwd_bwd computes
+ *   them (pad_idx, exclude_idx, dur_den, grad_scale as there), d_out [B Q, K + 1] = d(total) / d(out) * grad_scale, and
+ *   d_fused [B S, H] (row stride ld_dfused) = (add != 0 ? d_fused : 0) + gscale * pool^T(d_out . w_head).  The loss partials go
+ *   to ws (r3d_losses_ws_floats(B, S, Q) floats, 16-byte aligned) in r3d_losses_fwd_bwd's unit layout
+ *   with the B S segmentation units written as zeros (no precondition on what ws held): reduce them with r3d_losses_finalize or r3d_adamw_flat*_fin and
+ *   has_seg = 0.  tick_a / tick_b (optional device int64) are incremented once per call.  No atomics; the same call gives
+ *   the same bits.
+ * r3d_afft_head_supported (host-only): H % 4 == 0, H <= 1024, Q <= 64, 2 <= n_head <= 1024 and Q * (H + n_head) floats
+ *   within 152 KiB of LDS.  A refused shape returns R3D_EINVAL before anything is enqueued; fused, pooled, w_head, d_fused
+ *   and ws 16-byte aligned, ld_fused and ld_dfused multiples of 4 (R3D_EALIGN). */
+typedef struct r3d_afft_head_args {
+    const float* fused; int32_t ld_fused;
+    const float* w_head; const float* b_head; int32_t n_head;       /* n_head = K + 1 */
+    float* pooled; float* out; int32_t ld_out;
+    int32_t B, S, Q, K, H;
+    const int64_t* past_label; const int64_t* target; const float* target_dur;
+    int32_t pad_idx, exclude_idx;
+    const float* dur_den; float grad_scale;
+    float* d_out; int32_t ld_dout;
+    float* d_fused; int32_t ld_dfused; float gscale; int32_t add;
+    int64_t* tick_a; int64_t* tick_b;
+} r3d_afft_head_args;
+int r3d_afft_head_supported(int H, int Q, int n_head);
+int r3d_afft_head_fwd(const r3d_afft_head_args* args, void* stream);
+int r3d_afft_head_step(const r3d_afft_head_args* args, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

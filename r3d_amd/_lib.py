@@ -162,6 +162,17 @@ class ClipCollateJob(C.Structure):
                 [(n, C.c_void_p) for n in "features depth past_label trans_future_dur trans_future_target".split()])
 
 
+class AfftHeadArgs(C.Structure):
+    """struct r3d_afft_head_args"""
+    _fields_ = [("fused", C.c_void_p), ("ld_fused", C.c_int32), ("w_head", C.c_void_p), ("b_head", C.c_void_p),
+                ("n_head", C.c_int32), ("pooled", C.c_void_p), ("out", C.c_void_p), ("ld_out", C.c_int32),
+                ("B", C.c_int32), ("S", C.c_int32), ("Q", C.c_int32), ("K", C.c_int32), ("H", C.c_int32),
+                ("past_label", C.c_void_p), ("target", C.c_void_p), ("target_dur", C.c_void_p), ("pad_idx", C.c_int32),
+                ("exclude_idx", C.c_int32), ("dur_den", C.c_void_p), ("grad_scale", C.c_float), ("d_out", C.c_void_p),
+                ("ld_dout", C.c_int32), ("d_fused", C.c_void_p), ("ld_dfused", C.c_int32), ("gscale", C.c_float),
+                ("add", C.c_int32), ("tick_a", C.c_void_p), ("tick_b", C.c_void_p)]
+
+
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 
 _I, _L, _F, _P, _D = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_double
@@ -306,6 +317,9 @@ _SIGNATURES = {
     "r3d_tcontrast_ws_floats": ([_I, _I], C.c_int64),
     "r3d_tcontrast_fwd": ([_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P], C.c_int),
     "r3d_tcontrast_bwd": ([_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _F, _P, _I, _I, _P], C.c_int),
+    "r3d_afft_head_supported": ([_I, _I, _I], C.c_int),
+    "r3d_afft_head_fwd": ([_P, _P], C.c_int),
+    "r3d_afft_head_step": ([_P, _P, _P], C.c_int),
     "r3d_focal_rows": ([_P, _I, _P, _I, _I, _L, _I, _L, _F, _F, _F, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P], C.c_int),
 }
 

@@ -6,6 +6,7 @@
 //     [floor(q S / Q), ceil((q + 1) S / Q)), and its adjoint.
 // Rows are ordered (clip, frame) b-major like everywhere in this library: row = b * S + s.
 #include "common.h"
+#include "pool_dev.h"
 #include "../../include/r3d_hip.h"
 
 namespace r3d {
@@ -35,9 +36,6 @@ __global__ __launch_bounds__(256) void posenc_bwd_kernel(const float* __restrict
         dx[(size_t)r * lddx + c] = v;
     }
 }
-
-__device__ __forceinline__ int pool_start(int q, int S, int Q) { return (int)(((long long)q * S) / Q); }
-__device__ __forceinline__ int pool_end(int q, int S, int Q) { return (int)((((long long)(q + 1)) * S + Q - 1) / Q); }
 
 // y[b*Q + q, :] = mean_{s in window(q)} x[b*S + s, :]
 __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,

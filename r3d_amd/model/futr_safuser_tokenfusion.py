@@ -110,6 +110,17 @@ class FUTR(nn.Module):
     num_decoder_layers=6, query_num=49) -- model/futr_safuser_tokenfusion.py:103-152."""
 
     _fuser_cls = CMFuser                # (the BN-blend variant swaps in its own fuser, futr_safuser_batchnormalization.py)
+    # hooks of the models that share this constructor and forward (model/afft.py: no 'seg' output, fc_seg only with args.seg)
+    _out_names = ("duration", "action", "seg")
+    _seg_optional = False
+
+    @staticmethod
+    def _engine_cls():
+        return FusionEngine
+
+    @staticmethod
+    def _autograd_fn():
+        return _FusedForward
 
     def __init__(self, n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
                  num_decoder_layers=6, query_num=49, depth_pixels=224 * 224):
@@ -126,7 +137,10 @@ class FUTR(nn.Module):
         if getattr(args, "input_type", "i3d_transcript") != "i3d_transcript":
             raise NotImplementedError("only input_type='i3d_transcript' is built (the 'gt' embedding branch of "
                                       "futr_safuser_tokenfusion.py:150-152,180-182 is not on the RGB+Depth path)")
-        if not (getattr(args, "seg", True) and getattr(args, "anticipate", True)):
+        if self._seg_optional:
+            if not getattr(args, "anticipate", True):
+                raise NotImplementedError("anticipate=False leaves the reference's forward without any output")
+        elif not (getattr(args, "seg", True) and getattr(args, "anticipate", True)):
             raise NotImplementedError("the fused step implements seg=True and anticipate=True (opts.py:100-101 defaults)")
         if num_decoder_layers < 1:
             raise ValueError("num_decoder_layers must be >= 1")
@@ -137,8 +151,9 @@ class FUTR(nn.Module):
         self.query_attention = nn.MultiheadAttention(hidden_dim, n_head, batch_first=True)
         self.query_embed = nn.Embedding(self.n_query, hidden_dim)
         self.fuser = self._fuser_cls(dim=hidden_dim, depth=1, num_heads=n_head)
-        self.fc_seg = nn.Linear(hidden_dim, n_class)
-        nn.init.xavier_uniform_(self.fc_seg.weight)
+        if not self._seg_optional or getattr(args, "seg", False):
+            self.fc_seg = nn.Linear(hidden_dim, n_class)
+            nn.init.xavier_uniform_(self.fc_seg.weight)
         self.fc = nn.Linear(hidden_dim, n_class)
         nn.init.xavier_uniform_(self.fc.weight)
         self.fc_len = nn.Linear(hidden_dim, 1)
@@ -165,7 +180,7 @@ class FUTR(nn.Module):
             raise RuntimeError("r3d_amd.FUTR computes only on an MI355X through libr3d_hip.so; move the model to the "
                                "GPU with .to('cuda') (there is deliberately no CPU path).")
         if self._engine is None or self._engine.device != dev:
-            self._engine = FusionEngine(self, dev)
+            self._engine = self._engine_cls()(self, dev)
             ref = weakref.ref(self._engine)
             for p in self.parameters():
                 p._r3d_engine = ref              # lets r3d_amd.optim.FlatAdamW find the arena behind its parameters
@@ -185,8 +200,8 @@ class FUTR(nn.Module):
             return {k: v.clone() for k, v in out.items()}
         names = [n for n, _ in self.named_parameters()]
         params = [p for _, p in self.named_parameters()]
-        dur, act, seg = _FusedForward.apply(eng, src, depth_features, src_label, mode, self.training, names, *params)
-        return {"duration": dur, "action": act, "seg": seg}
+        outs = self._autograd_fn().apply(eng, src, depth_features, src_label, mode, self.training, names, *params)
+        return dict(zip(self._out_names, outs))
 
 
 class _FusedForward(torch.autograd.Function):

@@ -1540,3 +1540,57 @@ def focal_rows(pred, gold, pad_idx, *, exclude_idx=None, alpha=1.0, gamma=2.0, p
                                      float(alpha), float(gamma), float(penalty_weight), _p(ws), _p(loss_out), _p(flags),
                                      _p(counts), _p(d_loss), float(gscale), _p(d_pred), _ld(d_pred) if d_pred is not None else 0,
                                      1 if add else 0, _stream()), "r3d_focal_rows")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# AFFT baseline: the pooled-head chain (csrc/afft.hip)
+# ----------------------------------------------------------------------------------------------------------
+def afft_head_supported(H, Q, n_head):
+    return bool(_lib.load().r3d_afft_head_supported(H, Q, n_head))
+
+
+def _afft_check(fused, w_head, b_head, pooled, out, B, S, Q):
+    n_head, H = w_head.shape
+    if not afft_head_supported(H, Q, n_head):
+        raise ValueError(f"hidden {H}, {Q} queries, {n_head} head outputs: the pooled-head chain takes hidden % 4 == 0, "
+                         f"hidden <= 1024, n_query <= 64, <= 1024 head outputs and keeps n_query * (hidden + head outputs) "
+                         f"floats in LDS (<= 152 KiB)")
+    for t in (fused, w_head, b_head, pooled, out):
+        _f32(t)
+    assert B > 0 and S > 0 and fused.shape == (B * S, H) and fused.stride(1) == 1
+    assert w_head.is_contiguous() and b_head.is_contiguous() and b_head.numel() == n_head
+    assert pooled.is_contiguous() and pooled.shape == (B * Q, H) and out.shape == (B * Q, n_head) and out.stride(1) == 1
+    a = _lib.AfftHeadArgs()
+    a.fused, a.ld_fused, a.w_head, a.b_head, a.n_head = fused.data_ptr(), _ld(fused), w_head.data_ptr(), b_head.data_ptr(), n_head
+    a.pooled, a.out, a.ld_out = pooled.data_ptr(), out.data_ptr(), _ld(out)
+    a.B, a.S, a.Q, a.K, a.H = B, S, Q, n_head - 1, H
+    return a
+
+
+def afft_head_fwd(fused, w_head, b_head, pooled, out, B, S, Q):
+    """pooled [B Q, H] = adaptive_avg_pool1d over each clip's S rows of fused [B S, H]; out [B Q, K + 1] = pooled . w_head^T
+    + b_head: one launch, one workgroup per clip."""
+    a = _afft_check(fused, w_head, b_head, pooled, out, B, S, Q)
+    check(_lib.load().r3d_afft_head_fwd(C.byref(a), _stream()), "r3d_afft_head_fwd")
+
+
+def afft_head_step(fused, w_head, b_head, pooled, out, B, S, Q, past_label, target, target_dur, pad_idx, exclude_idx, d_out,
+                   d_fused, ws, *, dur_den=None, grad_scale=1.0, gscale=1.0, add=False, tick_a=None, tick_b=None):
+    """afft_head_fwd, the clip's anticipation CE rows and duration unit (the arithmetic of losses_fwd_bwd), d_out and
+    d_fused = (d_fused if add else 0) + gscale * d loss / d fused in one launch.  The loss partials stay in ws
+    (losses_ws_floats(B, S, Q) floats; every unit is rewritten, the segmentation ones with zeros): reduce them with losses_finalize(loss_finalize_job(ws, B, S, Q,
+    False, ...)) or hand that job to adamw_flat(loss_fin=...)."""
+    a = _afft_check(fused, w_head, b_head, pooled, out, B, S, Q)
+    n_head, H = w_head.shape
+    assert past_label.dtype == torch.int64 and target.dtype == torch.int64 and target_dur.dtype == torch.float32
+    assert past_label.is_cuda and target.is_cuda and target_dur.is_cuda
+    assert past_label.is_contiguous() and target.is_contiguous() and target_dur.is_contiguous()
+    assert past_label.numel() == B * S and target.numel() == B * Q and target_dur.numel() == B * Q
+    _f32(d_out), _f32(d_fused), _f32(ws)
+    assert d_out.shape == (B * Q, n_head) and d_out.stride(1) == 1 and d_fused.shape == (B * S, H) and d_fused.stride(1) == 1
+    assert ws.numel() >= losses_ws_floats(B, S, Q)
+    a.past_label, a.target, a.target_dur = past_label.data_ptr(), target.data_ptr(), target_dur.data_ptr()
+    a.pad_idx, a.exclude_idx, a.dur_den, a.grad_scale = pad_idx, exclude_idx, _pv(dur_den), grad_scale
+    a.d_out, a.ld_dout, a.d_fused, a.ld_dfused = d_out.data_ptr(), _ld(d_out), d_fused.data_ptr(), _ld(d_fused)
+    a.gscale, a.add, a.tick_a, a.tick_b = gscale, 1 if add else 0, _pv(tick_a), _pv(tick_b)
+    check(_lib.load().r3d_afft_head_step(C.byref(a), _p(ws), _stream()), "r3d_afft_head_step")
