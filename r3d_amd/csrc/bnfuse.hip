@@ -8,14 +8,15 @@
 //             are the BatchNorm / alpha parameter gradients (summed by r3d_rowmod_sum_batched) -> BatchNorm input
 //             gradient (+ the ReLU of the RGB embedding :194).
 // Row kernels: one workgroup (2 waves = the two modality tokens) per frame; column statistics: one workgroup per 64
-// channels.  All loads unconditional from clamped columns, issued up front; fixed-order reductions.
+// channels.  All loads unconditional from clamped columns, issued up front; fixed-order reductions.  norm1's forward tail and
+// backward row are seam_rows.h's; here are the blend, its adjoint, the statistics, the apply and the sync kernels.
 #include "common.h"
 #include "../../include/r3d_hip.h"
+#include "seam_rows.h"
 
 namespace r3d {
 
 constexpr float kEpsBN = 1e-5f;
-constexpr float kEpsLN = 1e-5f;
 
 // ---- statistics: x [2][N][C] given as two pointers.  out: mean [2][C], rstd [2][C], absgamma [2][C].
 struct BnStatsArgs {
@@ -95,38 +96,26 @@ template <int EPL>
 __global__ __launch_bounds__(128) void bn_blend_fwd_kernel(const BnBlendArgs a) {
     const int n = blockIdx.x, lane = threadIdx.x & 63, t = threadIdx.x >> 6, C = a.C;
     const size_t rowo = (size_t)n * C, row = (size_t)2 * n + t;
+    int cc[EPL];
+    seam_cols<EPL>(lane, C, cc);
     float x[EPL], g1[EPL], b1[EPL];
-    float s1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e, cc = c < C ? c : C - 1;
-        const float r = a.rgb[rowo + cc], d = a.dep[rowo + cc];
-        const float rb = (r - a.mean[cc]) * a.rstd[cc] * a.g_r[cc] + a.b_r[cc];
-        const float db = (d - a.mean[C + cc]) * a.rstd[C + cc] * a.g_d[cc] + a.b_d[cc];
-        const float al = a.alpha[cc];
-        const float own = t == 0 ? rb : db, oth = t == 0 ? db : rb;
-        const float sel = (t == 0 ? a.m_rgb : a.m_dep)[cc];
-        const float keep = a.drop ? a.drop_scale * (float)a.drop[row * C + cc] : 1.f;
-        float v = (sel != 0.f ? al * own + (1.f - al) * oth : own) * keep;
-        if (c >= C) v = 0.f;
-        x[e] = v; s1 += v;
-        g1[e] = a.ln1_g[cc]; b1[e] = a.ln1_b[cc];
-        if (c < C) a.x0[row * C + c] = v;
-    }
-    const float mean1 = wave_sum(s1) / (float)C;
-    float q1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const float dl = (lane + 64 * e < C) ? x[e] - mean1 : 0.f;
-        q1 += dl * dl;
-    }
-    const float rstd1 = 1.0f / sqrtf(wave_sum(q1) / (float)C + kEpsLN);
-    if (lane == 0) { a.m1[row] = mean1; a.r1[row] = rstd1; }
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        if (c < C) a.h1[row * C + c] = (x[e] - mean1) * rstd1 * g1[e] + b1[e];
+        const float r = a.rgb[rowo + cc[e]], d = a.dep[rowo + cc[e]];
+        const float rb = (r - a.mean[cc[e]]) * a.rstd[cc[e]] * a.g_r[cc[e]] + a.b_r[cc[e]];
+        const float db = (d - a.mean[C + cc[e]]) * a.rstd[C + cc[e]] * a.g_d[cc[e]] + a.b_d[cc[e]];
+        const float al = a.alpha[cc[e]];
+        const float own = t == 0 ? rb : db, oth = t == 0 ? db : rb;
+        const float sel = (t == 0 ? a.m_rgb : a.m_dep)[cc[e]];
+        const float keep = a.drop ? a.drop_scale * (float)a.drop[row * C + cc[e]] : 1.f;
+        float v = (sel != 0.f ? al * own + (1.f - al) * oth : own) * keep;
+        if (c >= C) v = 0.f;
+        x[e] = v;
+        g1[e] = a.ln1_g[cc[e]]; b1[e] = a.ln1_b[cc[e]];
+        if (c < C) a.x0[row * C + c] = v;
     }
+    seam_norm1_fwd<EPL>(x, g1, b1, a.m1, a.r1, a.h1, row, lane, C);
 }
 
 template <int EPL>
@@ -136,41 +125,13 @@ __global__ __launch_bounds__(128) void bn_blend_bwd_kernel(const BnBlendArgs a) 
     float* G = lds;
     float* P = lds + 2 * C;
     const size_t rowo = (size_t)n * C, row = (size_t)2 * n + t;
-    const float mean1 = a.m1[row], rstd1 = a.r1[row];
-    float xh[EPL], gg[EPL], a1[EPL], keep[EPL], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e, cc = c < C ? c : C - 1;
-        const float dh = a.d_h1[row * C + cc], xv = a.x0[row * C + cc];
-        a1[e] = a.add1 ? a.add1[row * C + cc] : 0.f;
-        keep[e] = a.drop ? a.drop_scale * (float)a.drop[row * C + cc] : 1.f;
-        float xhat = 0.f, g = 0.f;
-        if (c < C) {
-            xhat = (xv - mean1) * rstd1;
-            g = dh * a.ln1_g[cc];
-            P[(t * 2 + 0) * C + c] = dh * xhat;
-            P[(t * 2 + 1) * C + c] = dh;
-        }
-        xh[e] = xhat; gg[e] = g; s1 += g; s2 += g * xhat;
-    }
-    s1 = wave_sum(s1) / (float)C; s2 = wave_sum(s2) / (float)C;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < C) G[t * C + c] = (rstd1 * (gg[e] - s1 - xh[e] * s2) + a1[e]) * keep[e];
-    }
+    int cc[EPL];
+    seam_cols<EPL>(lane, C, cc);
+    SeamRowBwd<EPL, false, false> tk;
+    tk.load(a.d_h1, a.x0, a.m1, a.r1, a.ln1_g, a.add1, nullptr, a.drop, a.drop_scale, row, C, cc);
+    tk.norm1_bwd(G, P, t, lane, C, cc);
     __syncthreads();
-    if (t == 1) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const int c = lane + 64 * e;
-            if (c < C) {
-                a.ws_n1[((size_t)n * 2 + 0) * C + c] = P[0 * C + c] + P[2 * C + c];
-                a.ws_n1[((size_t)n * 2 + 1) * C + c] = P[1 * C + c] + P[3 * C + c];
-            }
-        }
-        return;
-    }
+    if (t == 1) { seam_norm1_partials<EPL>(P, a.ws_n1, n, lane, C); return; }
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
@@ -282,13 +243,6 @@ R3D_EXPORT int r3d_bn_stats(const float* x_rgb, const float* x_dep, float* run_m
     return R3D_OK;
 }
 
-template <typename K>
-static void bn_launch(K k2, K k8, K k16, int C, dim3 grid, size_t shmem, hipStream_t s, const BnBlendArgs& a) {
-    if (C <= 128) hipLaunchKernelGGL(k2, grid, dim3(128), shmem, s, a);
-    else if (C <= 512) hipLaunchKernelGGL(k8, grid, dim3(128), shmem, s, a);
-    else hipLaunchKernelGGL(k16, grid, dim3(128), shmem, s, a);
-}
-
 /* Forward seam of the BN-blend fuser: x0 [2N, C] = dropout(blend(BN(rgb), BN(dep))), h1 = norm1(x0), m1 / r1 [2N]. */
 R3D_EXPORT int r3d_bn_blend_fwd(const float* rgb, const float* dep, const float* mean, const float* rstd,
                                 const float* gamma_rgb, const float* beta_rgb, const float* gamma_dep, const float* beta_dep,
@@ -301,7 +255,8 @@ R3D_EXPORT int r3d_bn_blend_fwd(const float* rgb, const float* dep, const float*
     a.rgb = rgb; a.dep = dep; a.mean = mean; a.rstd = rstd; a.g_r = gamma_rgb; a.b_r = beta_rgb; a.g_d = gamma_dep;
     a.b_d = beta_dep; a.alpha = alpha; a.m_rgb = mask_rgb; a.m_dep = mask_dep; a.drop = drop_mask; a.drop_scale = drop_scale;
     a.ln1_g = ln1_gamma; a.ln1_b = ln1_beta; a.x0 = x0; a.h1 = h1; a.m1 = m1; a.r1 = r1; a.N = N; a.C = C;
-    bn_launch(bn_blend_fwd_kernel<2>, bn_blend_fwd_kernel<8>, bn_blend_fwd_kernel<16>, C, dim3(N), 0, (hipStream_t)stream, a);
+    seam_launch(bn_blend_fwd_kernel<2>, bn_blend_fwd_kernel<8>, bn_blend_fwd_kernel<16>, C, dim3(N), dim3(128), 0,
+                (hipStream_t)stream, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }
@@ -324,8 +279,8 @@ R3D_EXPORT int r3d_bn_blend_bwd(const float* d_h1, const float* x0, const float*
     a.ln1_g = ln1_gamma; a.x0 = const_cast<float*>(x0); a.m1 = const_cast<float*>(m1); a.r1 = const_cast<float*>(r1);
     a.d_h1 = d_h1; a.add1 = add1; a.t_drb = t_drb; a.t_drbx = t_drbx; a.t_ddb = t_ddb; a.t_ddbx = t_ddbx; a.t_dal = t_dal;
     a.ws_n1 = ws_n1; a.N = N; a.C = C;
-    bn_launch(bn_blend_bwd_kernel<2>, bn_blend_bwd_kernel<8>, bn_blend_bwd_kernel<16>, C, dim3(N), (size_t)6 * C * sizeof(float),
-              (hipStream_t)stream, a);
+    seam_launch(bn_blend_bwd_kernel<2>, bn_blend_bwd_kernel<8>, bn_blend_bwd_kernel<16>, C, dim3(N), dim3(128),
+                (size_t)6 * C * sizeof(float), (hipStream_t)stream, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }

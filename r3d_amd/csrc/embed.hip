@@ -5,7 +5,9 @@
 //             (transformerblock.py:122).   Replaces 4 dependent launches (reduce, LN, exchange, LN) by one.
 //   backward: norm1 backward (+ the two residual gradients) -> exchange backward (index_put / clone, ReLU of :183)
 //             -> depth LayerNorm + ReLU backward.   Replaces 3 dependent launches by one.
-// The forward kernel is a template in embed_seam.h (plainfuse.hip instantiates its token-add form).
+// The forward kernel is a template in embed_seam.h (plainfuse.hip instantiates its token-add form).  What every fuser seam
+// does alike -- column setup, width dispatch, norm1 forward and backward rows, the depth LayerNorm backward -- is in
+// seam_rows.h; here are the exchange and its adjoint.
 // One workgroup (4 waves) per frame row n.  Everything is latency: all loads are unconditional (clamped columns) and
 // issued up front.  Reductions are wave shuffles / fixed-order LDS sums -> bitwise reproducible.
 #include "common.h"
@@ -32,94 +34,35 @@ __global__ __launch_bounds__(128) void embed_fuse_bwd_kernel(const EmbedBwdArgs 
     float* P = lds + 2 * H;
     const size_t row = (size_t)2 * n + t, rowo = (size_t)n * H;
     int cc[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) { const int c = lane + 64 * e; cc[e] = c < H ? c : H - 1; }
+    seam_cols<EPL>(lane, H, cc);
     // ---- every load of the workgroup up front
-    const float mean1 = a.m1[row], rstd1 = a.r1[row];
-    float dh[EPL], xv[EPL], g1[EPL], a1[EPL], a2[EPL], keep[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        dh[e] = a.d_h1[row * H + cc[e]];
-        xv[e] = a.x0[row * H + cc[e]];
-        g1[e] = a.ln1_g[cc[e]];
-        a1[e] = a.add1 ? a.add1[row * H + cc[e]] : 0.f;
-        a2[e] = a.add2 ? a.add2[row * H + cc[e]] : 0.f;
-        keep[e] = a.drop ? a.drop_scale * (float)a.drop[row * H + cc[e]] : 1.f;
-    }
-    float mr[EPL], md[EPL], rg[EPL], dp[EPL], gd[EPL], bd[EPL];
-    float mean_d = 0.f, rstd_d = 0.f;
+    SeamRowBwd<EPL, true, true> tk;
+    tk.load(a.d_h1, a.x0, a.m1, a.r1, a.ln1_g, a.add1, a.add2, a.drop, a.drop_scale, row, H, cc);
+    SeamDepthLnBwd<EPL> dl;
+    float mr[EPL], md[EPL], rg[EPL];
     if (t == 0) {
-        mean_d = a.mean_d[n]; rstd_d = a.rstd_d[n];
+        dl.load(a.dep_pre, a.mean_d, a.rstd_d, a.lnd_g, a.lnd_b, n, H, cc);
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            mr[e] = a.m_rgb[cc[e]]; md[e] = a.m_dep[cc[e]];
-            rg[e] = a.rgb[rowo + cc[e]]; dp[e] = a.dep_pre[rowo + cc[e]];
-            gd[e] = a.lnd_g[cc[e]]; bd[e] = a.lnd_b[cc[e]];
-        }
+        for (int e = 0; e < EPL; ++e) { mr[e] = a.m_rgb[cc[e]]; md[e] = a.m_dep[cc[e]]; rg[e] = a.rgb[rowo + cc[e]]; }
     }
     // ---- norm1 backward of token t (+ the two residual gradients), then back through embd_drop
-    float xh[EPL], gg[EPL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        float xhat = 0.f, g = 0.f;
-        if (c < H) {
-            xhat = (xv[e] - mean1) * rstd1;
-            g = dh[e] * g1[e];
-            P[(t * 2 + 0) * H + c] = dh[e] * xhat;
-            P[(t * 2 + 1) * H + c] = dh[e];
-        }
-        xh[e] = xhat; gg[e] = g;
-        s1 += g; s2 += g * xhat;
-    }
-    s1 = wave_sum(s1) / (float)H;
-    s2 = wave_sum(s2) / (float)H;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < H) G[t * H + c] = (rstd1 * (gg[e] - s1 - xh[e] * s2) + a1[e] + a2[e]) * keep[e];
-    }
+    tk.norm1_bwd(G, P, t, lane, H, cc);
     __syncthreads();
-    if (t == 1) {                       // norm1 parameter-gradient partial of this frame (its two token rows)
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const int c = lane + 64 * e;
-            if (c < H) {
-                a.ws_n1[((size_t)n * 2 + 0) * H + c] = P[0 * H + c] + P[2 * H + c];
-                a.ws_n1[((size_t)n * 2 + 1) * H + c] = P[1 * H + c] + P[3 * H + c];
-            }
-        }
-        return;
-    }
+    if (t == 1) { seam_norm1_partials<EPL>(P, a.ws_n1, n, lane, H); return; }
     // ---- exchange backward (index_put / clone), ReLU of the RGB embedding, depth LayerNorm + ReLU backward
-    float xd[EPL], gq[EPL];
-    float u1 = 0.f, u2 = 0.f;
+    // (the gate is a 0/1 product: a gated-off negative gradient is -0.0, where plainfuse.hip's select gives +0.0)
+    float dd[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        float xhat = 0.f, g = 0.f;
+        dd[e] = 0.f;
         if (c < H) {
             const float g0 = G[c], g1v = G[H + c];
-            const float drgb = ((mr[e] != 0.f ? 0.f : g0) + (md[e] != 0.f ? g1v : 0.f)) * (rg[e] > 0.f ? 1.f : 0.f);
-            a.d_rgb_pre[rowo + c] = drgb;
-            float dd = (mr[e] != 0.f ? g0 : 0.f) + (md[e] != 0.f ? 0.f : g1v);
-            xhat = (dp[e] - mean_d) * rstd_d;
-            if (!(xhat * gd[e] + bd[e] > 0.f)) dd = 0.f;
-            a.ws_dep[((size_t)n * 2 + 0) * H + c] = dd * xhat;
-            a.ws_dep[((size_t)n * 2 + 1) * H + c] = dd;
-            g = dd * gd[e];
+            a.d_rgb_pre[rowo + c] = ((mr[e] != 0.f ? 0.f : g0) + (md[e] != 0.f ? g1v : 0.f)) * (rg[e] > 0.f ? 1.f : 0.f);
+            dd[e] = (mr[e] != 0.f ? g0 : 0.f) + (md[e] != 0.f ? 0.f : g1v);
         }
-        xd[e] = xhat; gq[e] = g;
-        u1 += g; u2 += g * xhat;
     }
-    u1 = wave_sum(u1) / (float)H;
-    u2 = wave_sum(u2) / (float)H;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < H) a.d_dep_pre[rowo + c] = rstd_d * (gq[e] - u1 - xd[e] * u2);
-    }
+    dl.ln_relu_bwd(dd, a.d_dep_pre, a.ws_dep, n, lane, H);
 }
 
 }  // namespace r3d
@@ -140,11 +83,8 @@ R3D_EXPORT int r3d_embed_fuse_bwd(const float* d_h1, const float* x0, const floa
     R3D_REQUIRE(lnd_gamma && lnd_beta && d_rgb_pre && d_dep_pre && ws_n1 && ws_dep && N > 0 && H > 0 && H <= 1024);
     EmbedBwdArgs a{d_h1, x0, m1, r1, ln1_gamma, add1, add2, drop_mask, drop_scale, mask_rgb, mask_dep, rgb, dep_pre,
                    mean_d, rstd_d, lnd_gamma, lnd_beta, d_rgb_pre, d_dep_pre, ws_n1, ws_dep, N, H};
-    const size_t shmem = (size_t)6 * H * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
-    if (H <= 128) hipLaunchKernelGGL(embed_fuse_bwd_kernel<2>, dim3(N), dim3(128), shmem, s, a);
-    else if (H <= 512) hipLaunchKernelGGL(embed_fuse_bwd_kernel<8>, dim3(N), dim3(128), shmem, s, a);
-    else hipLaunchKernelGGL(embed_fuse_bwd_kernel<16>, dim3(N), dim3(128), shmem, s, a);
+    seam_launch(embed_fuse_bwd_kernel<2>, embed_fuse_bwd_kernel<8>, embed_fuse_bwd_kernel<16>, H, dim3(N), dim3(128),
+                (size_t)6 * H * sizeof(float), (hipStream_t)stream, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }

@@ -1,13 +1,13 @@
 // The forward seam kernel of embed.hip (token fusion: exchange) and plainfuse.hip (plain SA-Fuser: + modality token),
-// one template instantiated by both translation units.  See embed.hip's header for what it computes.
+// one template instantiated by both translation units.  See embed.hip's header for what it computes.  Its own part is the
+// slab sums and the depth LayerNorm forward; the norm1 tail of the token row is seam_rows.h's.
 #pragma once
 #include "common.h"
 #include "../../include/r3d_hip.h"
 #include "chain_bf3.h"
+#include "seam_rows.h"
 
 namespace r3d {
-
-constexpr float kLnEpsE = 1e-5f;
 
 struct EmbedFwdArgs {
     const float* rgb_src; int ns_r; const float* bias_r;      // ns_r > 0: [ns_r][N][H] slabs, bias + ReLU applied here
@@ -32,8 +32,7 @@ __global__ __launch_bounds__(256) void embed_fuse_fwd_kernel(const EmbedFwdArgs 
     const int n = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, H = a.H;
     const size_t stride = (size_t)a.N * H, rowo = (size_t)n * H;
     int cc[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) { const int c = lane + 64 * e; cc[e] = c < H ? c : H - 1; }
+    seam_cols<EPL>(lane, H, cc);
     // ---- operands of the row tail, prefetched by the two waves that run it (wave t finishes token t of the frame)
     const int t = wave & 1;
     float g1[EPL], b1[EPL], gd[EPL], bd[EPL], br[EPL], bdp[EPL], msk[EPL], keep[EPL];
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(256) void embed_fuse_fwd_kernel(const EmbedFwdArgs 
         const float dl = c < H ? dpre[e] - mean : 0.f;
         q += dl * dl;
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + kLnEpsE);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + kSeamLnEps);
     float d[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) d[e] = fmaxf((dpre[e] - mean) * rstd * gd[e] + bd[e], 0.f);
@@ -223,7 +222,6 @@ __global__ __launch_bounds__(256) void embed_fuse_fwd_kernel(const EmbedFwdArgs 
     // ---- token t of the frame: exchange (kTok: + modality token instead), embd_drop, norm1
     const size_t row = (size_t)2 * n + t;
     float x[EPL];
-    float s1 = 0.f;
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
@@ -233,24 +231,9 @@ __global__ __launch_bounds__(256) void embed_fuse_fwd_kernel(const EmbedFwdArgs 
         else v = (msk[e] != 0.f ? other : own) * keep[e];
         if (c >= H) v = 0.f;
         x[e] = v;
-        s1 += v;
         if (c < H) a.x0[row * H + c] = v;
     }
-    const float mean1 = wave_sum(s1) / (float)H;
-    float q1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        const float dl = c < H ? x[e] - mean1 : 0.f;
-        q1 += dl * dl;
-    }
-    const float rstd1 = 1.0f / sqrtf(wave_sum(q1) / (float)H + kLnEpsE);
-    if (lane == 0) { a.m1[row] = mean1; a.r1[row] = rstd1; }
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < H) a.h1[row * H + c] = (x[e] - mean1) * rstd1 * g1[e] + b1[e];
-    }
+    seam_norm1_fwd<EPL>(x, g1, b1, a.m1, a.r1, a.h1, row, lane, H);
 }
 
 /* Forward seam (see embed.hip's header).  rgb_src: ns_r > 0 -> split-K slabs [ns_r][N][H] of input_embed (bias_r and ReLU
@@ -264,11 +247,9 @@ static int embed_fuse_fwd_launch(EmbedFwdArgs a, hipStream_t s) {
     R3D_REQUIRE(kTok ? a.tok != nullptr : (a.m_rgb && a.m_dep));
     R3D_REQUIRE(a.rgb_out && a.dep_pre_out && a.mean_d && a.rstd_d && a.dep_out && a.x0 && a.h1 && a.m1 && a.r1);
     R3D_REQUIRE(a.N > 0 && a.H > 0 && a.H <= 1024 && a.ns_r >= 0 && a.ns_d >= 1);
-    const size_t shmem = (size_t)16 * a.H * sizeof(float);
     const int grid = a.N + (a.pl_jobs ? r3d_cdiv(a.pl_total, 4) : 0);
-    if (a.H <= 128) hipLaunchKernelGGL((embed_fuse_fwd_kernel<2, kTok>), dim3(grid), dim3(256), shmem, s, a);
-    else if (a.H <= 512) hipLaunchKernelGGL((embed_fuse_fwd_kernel<8, kTok>), dim3(grid), dim3(256), shmem, s, a);
-    else hipLaunchKernelGGL((embed_fuse_fwd_kernel<16, kTok>), dim3(grid), dim3(256), shmem, s, a);
+    seam_launch(embed_fuse_fwd_kernel<2, kTok>, embed_fuse_fwd_kernel<8, kTok>, embed_fuse_fwd_kernel<16, kTok>, a.H, dim3(grid),
+                dim3(256), (size_t)16 * a.H * sizeof(float), s, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }

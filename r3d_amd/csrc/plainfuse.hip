@@ -8,7 +8,9 @@
 //             row gradients, whose column sum is d modality_token.  That sum is left to a fixed-order reduction (a row-sum
 //             job of the grouped weight-gradient launch or of the LayerNorm-finalize launch): no atomics, bitwise the same
 //             from run to run.
-// One workgroup per frame: 4 waves forward (as embed.hip), 2 waves backward (the two tokens of the frame).
+// One workgroup per frame: 4 waves forward (as embed.hip), 2 waves backward (the two tokens of the frame).  The backward's
+// norm1 and depth LayerNorm rows are seam_rows.h's; here are the token partial and the ReLU gate.  Every load of the
+// workgroup is issued up front, from clamped columns, none under a data-dependent branch.
 #include "common.h"
 #include "../../include/r3d_hip.h"
 #include "embed_seam.h"
@@ -33,93 +35,42 @@ __global__ __launch_bounds__(128) void plain_fuse_bwd_kernel(const PlainBwdArgs 
     float* P = lds + 2 * H;
     const size_t row = (size_t)2 * n + t, rowo = (size_t)n * H;
     int cc[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) { const int c = lane + 64 * e; cc[e] = c < H ? c : H - 1; }
-    const float mean1 = a.m1[row], rstd1 = a.r1[row];
-    float dh[EPL], xv[EPL], g1[EPL], a1[EPL], keep[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        dh[e] = a.d_h1[row * H + cc[e]];
-        xv[e] = a.x0[row * H + cc[e]];
-        g1[e] = a.ln1_g[cc[e]];
-        a1[e] = a.add1 ? a.add1[row * H + cc[e]] : 0.f;
-        keep[e] = a.drop ? a.drop_scale * (float)a.drop[row * H + cc[e]] : 1.f;
-    }
-    float rg[EPL], dp[EPL], gd[EPL], bd[EPL];
-    float mean_d = 0.f, rstd_d = 0.f;
+    seam_cols<EPL>(lane, H, cc);
+    // ---- every load of the workgroup up front
+    SeamRowBwd<EPL, false, true> tk;
+    tk.load(a.d_h1, a.x0, a.m1, a.r1, a.ln1_g, a.add1, nullptr, a.drop, a.drop_scale, row, H, cc);
+    SeamDepthLnBwd<EPL> dl;
+    float rg[EPL];
     if (t == 0 && full) {
-        mean_d = a.mean_d[n]; rstd_d = a.rstd_d[n];
+        dl.load(a.dep_pre, a.mean_d, a.rstd_d, a.lnd_g, a.lnd_b, n, H, cc);
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            rg[e] = a.rgb[rowo + cc[e]]; dp[e] = a.dep_pre[rowo + cc[e]];
-            gd[e] = a.lnd_g[cc[e]]; bd[e] = a.lnd_b[cc[e]];
-        }
+        for (int e = 0; e < EPL; ++e) rg[e] = a.rgb[rowo + cc[e]];
     }
     // ---- norm1 backward of token t (+ the residual gradient), then back through embd_drop
-    float xh[EPL], gg[EPL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        float xhat = 0.f, g = 0.f;
-        if (c < H) {
-            xhat = (xv[e] - mean1) * rstd1;
-            g = dh[e] * g1[e];
-            P[(t * 2 + 0) * H + c] = dh[e] * xhat;
-            P[(t * 2 + 1) * H + c] = dh[e];
-        }
-        xh[e] = xhat; gg[e] = g;
-        s1 += g; s2 += g * xhat;
-    }
-    s1 = wave_sum(s1) / (float)H;
-    s2 = wave_sum(s2) / (float)H;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < H) G[t * H + c] = (rstd1 * (gg[e] - s1 - xh[e] * s2) + a1[e]) * keep[e];
-    }
+    tk.norm1_bwd(G, P, t, lane, H, cc);
     __syncthreads();
     if (t == 1) {                       // token partial and norm1 parameter-gradient partial of this frame
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
             const int c = lane + 64 * e;
-            if (c < H) {
-                a.t_tok[rowo + c] = G[c] + G[H + c];
-                if (full) {
-                    a.ws_n1[((size_t)n * 2 + 0) * H + c] = P[0 * H + c] + P[2 * H + c];
-                    a.ws_n1[((size_t)n * 2 + 1) * H + c] = P[1 * H + c] + P[3 * H + c];
-                }
-            }
+            if (c < H) a.t_tok[rowo + c] = G[c] + G[H + c];
         }
+        if (full) seam_norm1_partials<EPL>(P, a.ws_n1, n, lane, H);
         return;
     }
     if (!full) return;
     // ---- input_embed's ReLU gate; depth LayerNorm + ReLU backward
-    float xd[EPL], gq[EPL];
-    float u1 = 0.f, u2 = 0.f;
+    float dd[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        float xhat = 0.f, g = 0.f;
+        dd[e] = 0.f;
         if (c < H) {
             a.d_rgb_pre[rowo + c] = rg[e] > 0.f ? G[c] : 0.f;
-            float dd = G[H + c];
-            xhat = (dp[e] - mean_d) * rstd_d;
-            if (!(xhat * gd[e] + bd[e] > 0.f)) dd = 0.f;
-            a.ws_dep[((size_t)n * 2 + 0) * H + c] = dd * xhat;
-            a.ws_dep[((size_t)n * 2 + 1) * H + c] = dd;
-            g = dd * gd[e];
+            dd[e] = G[H + c];
         }
-        xd[e] = xhat; gq[e] = g;
-        u1 += g; u2 += g * xhat;
     }
-    u1 = wave_sum(u1) / (float)H;
-    u2 = wave_sum(u2) / (float)H;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < H) a.d_dep_pre[rowo + c] = rstd_d * (gq[e] - u1 - xd[e] * u2);
-    }
+    dl.ln_relu_bwd(dd, a.d_dep_pre, a.ws_dep, n, lane, H);
 }
 
 }  // namespace r3d
@@ -160,11 +111,8 @@ R3D_EXPORT int r3d_plain_fuse_bwd(const float* d_h1, const float* x0, const floa
     R3D_REQUIRE(!full || (rgb && dep_pre && mean_d && rstd_d && lnd_gamma && lnd_beta));
     PlainBwdArgs a{d_h1, x0, m1, r1, ln1_gamma, add1, drop_mask, drop_scale, rgb, dep_pre, mean_d, rstd_d, lnd_gamma,
                    lnd_beta, d_rgb_pre, d_dep_pre, ws_n1, ws_dep, t_tok, N, H};
-    const size_t shmem = (size_t)6 * H * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
-    if (H <= 128) hipLaunchKernelGGL(plain_fuse_bwd_kernel<2>, dim3(N), dim3(128), shmem, s, a);
-    else if (H <= 512) hipLaunchKernelGGL(plain_fuse_bwd_kernel<8>, dim3(N), dim3(128), shmem, s, a);
-    else hipLaunchKernelGGL(plain_fuse_bwd_kernel<16>, dim3(N), dim3(128), shmem, s, a);
+    seam_launch(plain_fuse_bwd_kernel<2>, plain_fuse_bwd_kernel<8>, plain_fuse_bwd_kernel<16>, H, dim3(N), dim3(128),
+                (size_t)6 * H * sizeof(float), (hipStream_t)stream, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }

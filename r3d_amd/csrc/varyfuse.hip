@@ -8,13 +8,13 @@
 //             input_embed's ReLU gate), d_dep (into the depth LayerNorm + ReLU backward), and one [N, C] term matrix whose
 //             column sum is d alpha.  The column sum is left to a fixed-order reduction (a row-sum job of the grouped
 //             weight-gradient launch or r3d_rowmod_sum_batched): no atomics, bitwise the same from run to run.
-// One workgroup (2 waves = the two modality tokens) per frame, as the BN-blend seam (bnfuse.hip).
+// One workgroup (2 waves = the two modality tokens) per frame, as the BN-blend seam (bnfuse.hip).  norm1's forward tail and
+// backward row are seam_rows.h's; here are the alpha-scaled exchange and its adjoint.
 #include "common.h"
 #include "../../include/r3d_hip.h"
+#include "seam_rows.h"
 
 namespace r3d {
-
-constexpr float kEpsVaryLN = 1e-5f;
 
 struct VaryArgs {
     const float* rgb; const float* dep;                         // [N][C] embeddings (post ReLU)
@@ -32,35 +32,23 @@ template <int EPL>
 __global__ __launch_bounds__(128) void vary_exchange_fwd_kernel(const VaryArgs a) {
     const int n = blockIdx.x, lane = threadIdx.x & 63, t = threadIdx.x >> 6, C = a.C;
     const size_t rowo = (size_t)n * C, row = (size_t)2 * n + t;
+    int cc[EPL];
+    seam_cols<EPL>(lane, C, cc);
     float x[EPL], g1[EPL], b1[EPL];
-    float s1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e, cc = c < C ? c : C - 1;
-        const float r = a.rgb[rowo + cc], d = a.dep[rowo + cc];
-        const float own = t == 0 ? r : d, oth = t == 0 ? d : r;
-        const float sel = (t == 0 ? a.m_rgb : a.m_dep)[cc];
-        const float keep = a.drop ? a.drop_scale * (float)a.drop[row * C + cc] : 1.f;
-        float v = (sel != 0.f ? a.alpha[cc] * oth : own) * keep;
-        if (c >= C) v = 0.f;
-        x[e] = v; s1 += v;
-        g1[e] = a.ln1_g[cc]; b1[e] = a.ln1_b[cc];
-        if (c < C) a.x0[row * C + c] = v;
-    }
-    const float mean1 = wave_sum(s1) / (float)C;
-    float q1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const float dl = (lane + 64 * e < C) ? x[e] - mean1 : 0.f;
-        q1 += dl * dl;
-    }
-    const float rstd1 = 1.0f / sqrtf(wave_sum(q1) / (float)C + kEpsVaryLN);
-    if (lane == 0) { a.m1[row] = mean1; a.r1[row] = rstd1; }
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        if (c < C) a.h1[row * C + c] = (x[e] - mean1) * rstd1 * g1[e] + b1[e];
+        const float r = a.rgb[rowo + cc[e]], d = a.dep[rowo + cc[e]];
+        const float own = t == 0 ? r : d, oth = t == 0 ? d : r;
+        const float sel = (t == 0 ? a.m_rgb : a.m_dep)[cc[e]];
+        const float keep = a.drop ? a.drop_scale * (float)a.drop[row * C + cc[e]] : 1.f;
+        float v = (sel != 0.f ? a.alpha[cc[e]] * oth : own) * keep;
+        if (c >= C) v = 0.f;
+        x[e] = v;
+        g1[e] = a.ln1_g[cc[e]]; b1[e] = a.ln1_b[cc[e]];
+        if (c < C) a.x0[row * C + c] = v;
     }
+    seam_norm1_fwd<EPL>(x, g1, b1, a.m1, a.r1, a.h1, row, lane, C);
 }
 
 template <int EPL>
@@ -70,40 +58,15 @@ __global__ __launch_bounds__(128) void vary_exchange_bwd_kernel(const VaryArgs a
     float* G = lds;
     float* P = lds + 2 * C;
     const size_t rowo = (size_t)n * C, row = (size_t)2 * n + t;
-    const float mean1 = a.m1[row], rstd1 = a.r1[row];
-    float xh[EPL], gg[EPL], a1[EPL], keep[EPL], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e, cc = c < C ? c : C - 1;
-        const float dh = a.d_h1[row * C + cc], xv = a.x0[row * C + cc];
-        a1[e] = a.add1 ? a.add1[row * C + cc] : 0.f;
-        keep[e] = a.drop ? a.drop_scale * (float)a.drop[row * C + cc] : 1.f;
-        float xhat = 0.f, g = 0.f;
-        if (c < C) {
-            xhat = (xv - mean1) * rstd1;
-            g = dh * a.ln1_g[cc];
-            P[(t * 2 + 0) * C + c] = dh * xhat;
-            P[(t * 2 + 1) * C + c] = dh;
-        }
-        xh[e] = xhat; gg[e] = g; s1 += g; s2 += g * xhat;
-    }
-    s1 = wave_sum(s1) / (float)C; s2 = wave_sum(s2) / (float)C;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < C) G[t * C + c] = (rstd1 * (gg[e] - s1 - xh[e] * s2) + a1[e]) * keep[e];
-    }
+    int cc[EPL];
+    seam_cols<EPL>(lane, C, cc);
+    SeamRowBwd<EPL, false, false> tk;
+    tk.load(a.d_h1, a.x0, a.m1, a.r1, a.ln1_g, a.add1, nullptr, a.drop, a.drop_scale, row, C, cc);
+    tk.norm1_bwd(G, P, t, lane, C, cc);
     __syncthreads();
     if (t == 1) {
         if (!a.ws_n1) return;                       // (the fuser chain's backward already left these partials)
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const int c = lane + 64 * e;
-            if (c < C) {
-                a.ws_n1[((size_t)n * 2 + 0) * C + c] = P[0 * C + c] + P[2 * C + c];
-                a.ws_n1[((size_t)n * 2 + 1) * C + c] = P[1 * C + c] + P[3 * C + c];
-            }
-        }
+        seam_norm1_partials<EPL>(P, a.ws_n1, n, lane, C);
         return;
     }
 #pragma unroll
@@ -118,13 +81,6 @@ __global__ __launch_bounds__(128) void vary_exchange_bwd_kernel(const VaryArgs a
         a.d_dep[rowo + c] = (sr ? al * g0 : 0.f) + (sd ? 0.f : g1v);
         a.t_dal[rowo + c] = (sr ? g0 * d : 0.f) + (sd ? g1v * r : 0.f);
     }
-}
-
-template <typename K>
-static void vary_launch(K k2, K k8, K k16, int C, dim3 grid, size_t shmem, hipStream_t s, const VaryArgs& a) {
-    if (C <= 128) hipLaunchKernelGGL(k2, grid, dim3(128), shmem, s, a);
-    else if (C <= 512) hipLaunchKernelGGL(k8, grid, dim3(128), shmem, s, a);
-    else hipLaunchKernelGGL(k16, grid, dim3(128), shmem, s, a);
 }
 
 }  // namespace r3d
@@ -143,8 +99,8 @@ R3D_EXPORT int r3d_scaled_exchange_fwd(const float* rgb, const float* dep, const
     a.rgb = rgb; a.dep = dep; a.alpha = alpha; a.m_rgb = mask_rgb; a.m_dep = mask_dep; a.drop = drop_mask;
     a.drop_scale = drop_scale; a.ln1_g = ln1_gamma; a.ln1_b = ln1_beta; a.x0 = x0; a.h1 = h1; a.m1 = m1; a.r1 = r1;
     a.N = N; a.C = C;
-    vary_launch(vary_exchange_fwd_kernel<2>, vary_exchange_fwd_kernel<8>, vary_exchange_fwd_kernel<16>, C, dim3(N), 0,
-                (hipStream_t)stream, a);
+    seam_launch(vary_exchange_fwd_kernel<2>, vary_exchange_fwd_kernel<8>, vary_exchange_fwd_kernel<16>, C, dim3(N), dim3(128),
+                0, (hipStream_t)stream, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }
@@ -166,7 +122,7 @@ R3D_EXPORT int r3d_scaled_exchange_bwd(const float* d_h1, const float* x0, const
     a.drop_scale = drop_scale; a.ln1_g = ln1_gamma; a.x0 = const_cast<float*>(x0); a.m1 = const_cast<float*>(m1);
     a.r1 = const_cast<float*>(r1); a.d_h1 = d_h1; a.add1 = add1; a.d_rgb_pre = d_rgb_pre; a.d_dep = d_dep; a.t_dal = t_dal;
     a.ws_n1 = ws_n1; a.N = N; a.C = C;
-    vary_launch(vary_exchange_bwd_kernel<2>, vary_exchange_bwd_kernel<8>, vary_exchange_bwd_kernel<16>, C, dim3(N),
+    seam_launch(vary_exchange_bwd_kernel<2>, vary_exchange_bwd_kernel<8>, vary_exchange_bwd_kernel<16>, C, dim3(N), dim3(128),
                 (size_t)6 * C * sizeof(float), (hipStream_t)stream, a);
     R3D_LAUNCH_CHECK();
     return R3D_OK;

@@ -719,21 +719,25 @@ def bn_blend_bwd(d_h1, x0, m1, r1, ln1_g, add1, drop, drop_scale, rgb, dep, mean
           "r3d_bn_blend_bwd")
 
 
-def _vary_check(N, Cc, rows_n, rows_2n, vecs, drop):
+def _seam_check(who, N, H, rows_n, rows_2n, vecs, drop):
+    """Operands of a fuser seam whose kernels hold a channel row in one wave's registers.  rows_n: [N, H] matrices;
+    rows_2n: (tensor, element count) pairs; vecs: [H] vectors; drop: the optional keep mask over x0's elements."""
+    if not 0 < H <= 1024:
+        raise ValueError(f"hidden {H}: the {who}'s seam holds a channel row in one wave's registers (<= 1024)")
     for t in rows_n:
-        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == N * Cc
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == N * H
     for t, k in rows_2n:
         assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == k
     for t in vecs:
-        assert t.is_contiguous() and t.numel() == Cc
-    assert drop is None or (drop.dtype == torch.uint8 and drop.numel() >= 2 * N * Cc)
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == H
+    assert drop is None or (drop.dtype == torch.uint8 and drop.numel() >= 2 * N * H)
 
 
 def scaled_exchange_fwd(rgb, dep, m_rgb, m_dep, alpha, drop, drop_scale, ln1_g, ln1_b, x0, h1, m1, r1):
     """Activation-magnitude fuser seam (csrc/varyfuse.hip): scaled exchange + embd_drop + norm1 -> x0, h1 [2N, C]."""
     N, Cc = rgb.shape
-    _vary_check(N, Cc, (rgb, dep), ((x0, 2 * N * Cc), (h1, 2 * N * Cc), (m1, 2 * N), (r1, 2 * N)),
-                (m_rgb, m_dep, alpha, ln1_g, ln1_b), drop)
+    _seam_check("activation-magnitude fuser", N, Cc, (rgb, dep),
+                ((x0, 2 * N * Cc), (h1, 2 * N * Cc), (m1, 2 * N), (r1, 2 * N)), (m_rgb, m_dep, alpha, ln1_g, ln1_b), drop)
     check(_lib.load().r3d_scaled_exchange_fwd(_p(rgb), _p(dep), _p(m_rgb), _p(m_dep), _p(alpha), _p(drop), drop_scale,
                                               _p(ln1_g), _p(ln1_b), _p(x0), _p(h1), _p(m1), _p(r1), N, Cc, _stream()),
           "r3d_scaled_exchange_fwd")
@@ -744,7 +748,8 @@ def scaled_exchange_bwd(d_h1, x0, m1, r1, ln1_g, add1, drop, drop_scale, rgb, de
     """Adjoint of scaled_exchange_fwd: d_rgb_pre (ReLU-gated), d_dep, and t_dal [N, C] whose column sum is d alpha."""
     N, Cc = rgb.shape
     big = [(d_h1, 2 * N * Cc), (x0, 2 * N * Cc), (m1, 2 * N), (r1, 2 * N)] + ([(add1, 2 * N * Cc)] if add1 is not None else [])
-    _vary_check(N, Cc, (rgb, dep, d_rgb_pre, d_dep, t_dal), big, (m_rgb, m_dep, alpha, ln1_g), drop)
+    _seam_check("activation-magnitude fuser", N, Cc, (rgb, dep, d_rgb_pre, d_dep, t_dal), big, (m_rgb, m_dep, alpha, ln1_g),
+                drop)
     assert ws_n1 is None or ws_n1.numel() >= 2 * N * Cc
     check(_lib.load().r3d_scaled_exchange_bwd(_p(d_h1), _p(x0), _p(m1), _p(r1), _p(ln1_g), _p(add1), _p(drop), drop_scale,
                                               _p(rgb), _p(dep), _p(m_rgb), _p(m_dep), _p(alpha), _p(d_rgb_pre), _p(d_dep),
@@ -815,26 +820,15 @@ def embed_fuse_bwd(d_h1, x0, m1, r1, ln1_g, add1, add2, drop, drop_scale, m_rgb,
                                          _stream()), "r3d_embed_fuse_bwd")
 
 
-def _plain_check(N, H, rows_n, rows_2n, vecs, drop):
-    if not 0 < H <= 1024:
-        raise ValueError(f"hidden {H}: the plain fuser's seam holds a channel row in one wave's registers (<= 1024)")
-    for t in rows_n:
-        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == N * H
-    for t, k in rows_2n:
-        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == k
-    for t in vecs:
-        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == H
-    assert drop is None or (drop.dtype == torch.uint8 and drop.numel() >= 2 * N * H)
-
-
 def plain_fuse_fwd(rgb_src, ns_r, bias_r, dep_src, ns_d, bias_d, lnd_g, lnd_b, tok, drop, drop_scale, ln1_g, ln1_b,
                    rgb_out, dep_pre_out, mean_d, rstd_d, dep_out, x0, h1, m1, r1, planes=None):
     """Plain SA-Fuser seam (csrc/plainfuse.hip): slab sums of both projections + bias / ReLU / depth LayerNorm + ReLU,
     x0 = embd_drop([rgb; dep] + tok), h1 = norm1(x0).  ns_r = 0: rgb_src is the finished embedding; ns_d >= 1 slabs
     (1: an already summed matrix).  planes (a WeightPlanes): its refresh() rides in the same launch."""
     N, H = dep_out.shape
-    _plain_check(N, H, (rgb_out, dep_pre_out, dep_out), ((x0, 2 * N * H), (h1, 2 * N * H), (m1, 2 * N), (r1, 2 * N),
-                                                         (mean_d, N), (rstd_d, N)), (lnd_g, lnd_b, tok, ln1_g, ln1_b), drop)
+    _seam_check("plain fuser", N, H, (rgb_out, dep_pre_out, dep_out),
+                ((x0, 2 * N * H), (h1, 2 * N * H), (m1, 2 * N), (r1, 2 * N), (mean_d, N), (rstd_d, N)),
+                (lnd_g, lnd_b, tok, ln1_g, ln1_b), drop)
     assert ns_r >= 0 and ns_d >= 1
     assert rgb_src.numel() >= max(ns_r, 1) * N * H and dep_src.numel() >= ns_d * N * H
     jobs, nj, nb = (planes.jobs_dev, planes.njobs, planes.blocks) if planes is not None else (None, 0, 0)
@@ -856,7 +850,7 @@ def plain_fuse_bwd(d_h1, x0, m1, r1, ln1_g, add1, drop, drop_scale, rgb, dep_pre
     big = [(d_h1, 2 * N * H), (x0, 2 * N * H), (m1, 2 * N), (r1, 2 * N)] + ([(add1, 2 * N * H)] if add1 is not None else [])
     rows = (t_tok,) + ((rgb, dep_pre, d_rgb_pre, d_dep_pre) if full else ())
     vecs = (ln1_g,) + ((lnd_g, lnd_b) if full else ())
-    _plain_check(N, H, rows, big + ([(mean_d, N), (rstd_d, N)] if full else []), vecs, drop)
+    _seam_check("plain fuser", N, H, rows, big + ([(mean_d, N), (rstd_d, N)] if full else []), vecs, drop)
     assert not full or (ws_n1.numel() >= 2 * N * H and ws_dep.numel() >= 2 * N * H)
     check(_lib.load().r3d_plain_fuse_bwd(_p(d_h1), _p(x0), _p(m1), _p(r1), _p(ln1_g), _p(add1), _p(drop), drop_scale,
                                          _p(rgb), _p(dep_pre), _p(mean_d), _p(rstd_d), _p(lnd_g), _p(lnd_b), _p(d_rgb_pre),

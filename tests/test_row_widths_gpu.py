@@ -589,3 +589,70 @@ def test_decoder_tail_losses_one_launch(ops, H, B, S, K):
     for k in ("out", "loss", "d_seg", "d_out", "dx", "dx2", "dgF", "dbF", "dg3", "db3"):
         close_rel(one[k], three[k].double(), f"{tag}: one launch vs three, {k}", rtol=1e-5)
     assert torch.equal(one["counts"], three["counts"]), tag
+
+
+# ----------------------------------------------------------------------------------------------------------
+# the four seams' optional operands (seam_rows.h): absent = present and neutral
+# ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H", [40, 136, 520])              # a partly filled last slot in each of the EPL 2 / 8 / 16 brackets
+def test_seam_absent_operand_equals_a_neutral_one(ops, H):
+    """A residual gradient (add1, add2) left out must give what an all-zero one gives, and a keep mask left out what an
+    all-ones mask with drop_scale 1 gives, output for output (torch.equal: -0.0 == 0.0 is intended), for the four backward
+    seams and the forward seams that take the mask."""
+    N = 3
+    f = lambda *s: torch.full(s, float("nan"), device="cuda")          # noqa: E731
+    rgb, dep = d(rnd(N, H, seed=1).relu()), d(rnd(N, H, seed=2).relu())
+    dpre = d(rnd(N, H, seed=3))
+    lg, lb, g1, b1 = d(1 + 0.2 * rnd(H, seed=4)), d(0.1 * rnd(H, seed=5)), d(1 + 0.2 * rnd(H, seed=6)), d(0.1 * rnd(H, seed=7))
+    mr, md = (d(m) for m in chan_masks(H, 8))
+    tok, al = d(0.3 * rnd(H, seed=9)), d(_alpha(H, 10))
+    dh1 = d(rnd(2 * N, H, seed=11))
+    zeros, ones = torch.zeros(2 * N, H, device="cuda"), torch.ones(2 * N, H, dtype=torch.uint8, device="cuda")
+    mean, rstd = d(0.1 * rnd(2, H, seed=12)), d(1 + 0.2 * rnd(2, H, seed=13).abs())
+    bn = [d(1 + 0.3 * rnd(H, seed=14)), d(0.1 * rnd(H, seed=15)), d(1 + 0.3 * rnd(H, seed=16)), d(0.1 * rnd(H, seed=17))]
+
+    def same(name, call, n_out, variants):
+        """call(outs, *operands) for each operand tuple of `variants`; every output must equal the first tuple's."""
+        got = []
+        for v in variants:
+            outs = [f(*s) for s in n_out]
+            call(outs, *v)
+            torch.cuda.synchronize()
+            got.append(outs)
+        for v, outs in zip(variants[1:], got[1:]):
+            for i, (a, b) in enumerate(zip(got[0], outs)):
+                assert not torch.isnan(a).any(), f"H{H} {name}: output {i} not fully written"
+                assert torch.equal(a, b), f"H{H} {name}: output {i} differs with {[None if t is None else 'given' for t in v]}"
+        return got[0]
+
+    rows, fr, pf = (2 * N, H), (N, H), (N,)
+    fwd_out = [fr, fr, pf, pf, fr, rows, rows, (2 * N,), (2 * N,)]          # rgb_out dep_pre mean_d rstd_d dep_out x0 h1 m1 r1
+    drops = [(None, 1.0), (ones, 1.0)]
+    e_f = same("embed_fuse_fwd", lambda o, dm, sc: ops.embed_fuse_fwd(rgb, 0, None, dpre.view(1, N, H), 1, None, lg, lb, mr, md,
+                                                                       dm, sc, g1, b1, *o), fwd_out, drops)
+    p_f = same("plain_fuse_fwd", lambda o, dm, sc: ops.plain_fuse_fwd(rgb, 0, None, dpre.view(1, N, H), 1, None, lg, lb, tok,
+                                                                       dm, sc, g1, b1, *o), fwd_out, drops)
+    row_out = [rows, rows, (2 * N,), (2 * N,)]                              # x0 h1 m1 r1
+    v_f = same("scaled_exchange_fwd", lambda o, dm, sc: ops.scaled_exchange_fwd(rgb, dep, mr, md, al, dm, sc, g1, b1, *o),
+               row_out, drops)
+    b_f = same("bn_blend_fwd", lambda o, dm, sc: ops.bn_blend_fwd(rgb, dep, mean, rstd, *bn, al, mr, md, dm, sc, g1, b1, *o),
+               row_out, drops)
+    adds = [(None, None, 1.0), (zeros, None, 1.0), (None, ones, 1.0), (zeros, ones, 1.0)]
+    _, dp_k, mean_d, rstd_d, _, x0, _, m1, r1 = e_f
+    same("embed_fuse_bwd", lambda o, a1, a2, dm, sc: ops.embed_fuse_bwd(dh1, x0, m1, r1, g1, a1, a2, dm, sc, mr, md, rgb, dp_k,
+                                                                         mean_d, rstd_d, lg, lb, *o),
+         [fr, fr, (N, 2, H), (N, 2, H)],
+         [(None, None, None, 1.0), (zeros, None, None, 1.0), (None, zeros, None, 1.0), (zeros, zeros, None, 1.0),
+          (None, None, ones, 1.0), (zeros, zeros, ones, 1.0)])
+    _, dp_k, mean_d, rstd_d, _, x0, _, m1, r1 = p_f
+    same("plain_fuse_bwd", lambda o, a1, dm, sc: ops.plain_fuse_bwd(dh1, x0, m1, r1, g1, a1, dm, sc, rgb, dp_k, mean_d, rstd_d,
+                                                                     lg, lb, *o),
+         [fr, fr, (N, 2, H), (N, 2, H), fr], adds)
+    x0, _, m1, r1 = v_f
+    same("scaled_exchange_bwd", lambda o, a1, dm, sc: ops.scaled_exchange_bwd(dh1, x0, m1, r1, g1, a1, dm, sc, rgb, dep, mr, md,
+                                                                               al, *o),
+         [fr, fr, fr, (N, 2, H)], adds)
+    x0, _, m1, r1 = b_f
+    same("bn_blend_bwd", lambda o, a1, dm, sc: ops.bn_blend_bwd(dh1, x0, m1, r1, g1, a1, dm, sc, rgb, dep, mean, rstd, *bn, al,
+                                                                 mr, md, *o),
+         [fr] * 5 + [(N, 2, H)], adds)
