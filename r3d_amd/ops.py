@@ -1249,45 +1249,61 @@ def embed_gather_bwd(d_out, idx, d_weight):
 # ----------------------------------------------------------------------------------------------------------
 # build-defined three-modality fuser pieces (csrc/fuser3.hip)
 # ----------------------------------------------------------------------------------------------------------
+def _f3_check(who, dense, drop=None, drop_shape=None):
+    """Operands of a three-modality fuser piece (csrc/fuser3.hip): dense: (tensor, shape) pairs, float32 device tensors
+    without strides; drop: the optional uint8 keep mask over x0's elements."""
+    for t, shape in dense:
+        assert t.dtype == torch.float32 and t.is_cuda, f"{who}: float32 device tensors only"
+        assert tuple(t.shape) == tuple(shape) and t.is_contiguous(), f"{who}: expected a contiguous {tuple(shape)}, got {tuple(t.shape)}"
+    if drop is not None:
+        assert drop.dtype == torch.uint8 and drop.is_cuda and tuple(drop.shape) == tuple(drop_shape) and drop.is_contiguous(), \
+            f"{who}: drop_mask must be a contiguous uint8 {tuple(drop_shape)} device tensor"
+
+
 def token_exchange3_fwd(xa, xb, xc, mask, x0, *, drop_mask=None, drop_scale=1.0):
     N, Cc = xa.shape
-    assert xb.shape == xa.shape == xc.shape and tuple(mask.shape) == (3, Cc) and tuple(x0.shape) == (3 * N, Cc)
-    for t in (xa, xb, xc, mask, x0):
-        assert t.is_contiguous()
+    _f3_check("token_exchange3_fwd", ((xa, (N, Cc)), (xb, (N, Cc)), (xc, (N, Cc)), (mask, (3, Cc)), (x0, (3 * N, Cc))),
+              drop_mask, (3 * N, Cc))
     check(_lib.load().r3d_token_exchange3_fwd(_p(xa), _p(xb), _p(xc), _p(mask), _p(drop_mask), drop_scale, _p(x0), N, Cc, _stream()),
           "r3d_token_exchange3_fwd")
 
 
 def token_exchange3_bwd(dx0, mask, da, db, dc, *, drop_mask=None, drop_scale=1.0):
     N, Cc = da.shape
-    assert tuple(dx0.shape) == (3 * N, Cc) and dx0.is_contiguous() and da.is_contiguous() and db.is_contiguous() and dc.is_contiguous()
+    _f3_check("token_exchange3_bwd", ((dx0, (3 * N, Cc)), (mask, (3, Cc)), (da, (N, Cc)), (db, (N, Cc)), (dc, (N, Cc))),
+              drop_mask, (3 * N, Cc))
     check(_lib.load().r3d_token_exchange3_bwd(_p(dx0), _p(mask), _p(drop_mask), drop_scale, _p(da), _p(db), _p(dc), N, Cc, _stream()),
           "r3d_token_exchange3_bwd")
 
 
-def attn3_fwd(qkv, probs, out, heads):
+def _attn3_dims(who, qkv):
     rows, C3 = qkv.shape
-    N, Cc = rows // 3, C3 // 3
-    assert qkv.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (rows, Cc) and probs.numel() == N * heads * 6
+    assert rows % 3 == 0 and C3 % 3 == 0, f"{who}: qkv must be [3 N, 3 C] (three token rows per frame, [q | k | v] columns)"
+    return rows, rows // 3, C3 // 3
+
+
+def attn3_fwd(qkv, probs, out, heads):
+    rows, N, Cc = _attn3_dims("attn3_fwd", qkv)
+    assert probs.numel() == N * heads * 6, "attn3_fwd: probs holds [N][heads][3][2]"
+    _f3_check("attn3_fwd", ((qkv, (rows, 3 * Cc)), (probs, probs.shape), (out, (rows, Cc))))
     check(_lib.load().r3d_attn3_fwd(_p(qkv), _p(probs), _p(out), N, Cc, heads, _stream()), "r3d_attn3_fwd")
 
 
 def attn3_bwd(qkv, d_out, d_qkv, heads):
-    rows, C3 = qkv.shape
-    N, Cc = rows // 3, C3 // 3
-    assert qkv.is_contiguous() and d_out.is_contiguous() and d_qkv.is_contiguous() and d_qkv.shape == qkv.shape
+    rows, N, Cc = _attn3_dims("attn3_bwd", qkv)
+    _f3_check("attn3_bwd", ((qkv, (rows, 3 * Cc)), (d_out, (rows, Cc)), (d_qkv, (rows, 3 * Cc))))
     check(_lib.load().r3d_attn3_bwd(_p(qkv), _p(d_out), _p(d_qkv), N, Cc, heads, _stream()), "r3d_attn3_bwd")
 
 
 def triple_mean_fwd(y, out):
     N, Cc = out.shape
-    assert tuple(y.shape) == (3 * N, Cc) and y.is_contiguous() and out.is_contiguous()
+    _f3_check("triple_mean_fwd", ((y, (3 * N, Cc)), (out, (N, Cc))))
     check(_lib.load().r3d_triple_mean_fwd(_p(y), _p(out), N, Cc, _stream()), "r3d_triple_mean_fwd")
 
 
 def triple_mean_bwd(d_out, dy):
     N, Cc = d_out.shape
-    assert tuple(dy.shape) == (3 * N, Cc) and dy.is_contiguous() and d_out.is_contiguous()
+    _f3_check("triple_mean_bwd", ((d_out, (N, Cc)), (dy, (3 * N, Cc))))
     check(_lib.load().r3d_triple_mean_bwd(_p(d_out), _p(dy), N, Cc, _stream()), "r3d_triple_mean_bwd")
 
 
