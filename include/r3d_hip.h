@@ -913,6 +913,34 @@ int r3d_afft_head_supported(int H, int Q, int n_head);
 int r3d_afft_head_fwd(const r3d_afft_head_args* args, void* stream);
 int r3d_afft_head_step(const r3d_afft_head_args* args, float* ws, void* stream);
 
+/* ---- CNN baseline: the segmentation-head step (csrc/cnn.hip; model/cnn.py of the reference: seg = fc_seg(x)) -------------
+ * One launch over the N = B S frame rows, one workgroup per 64 rows:
+ *   logits = x . w^T + b [N, Kseg], stored to seg (row stride ld_seg) when seg is not NULL;
+ *   unit r of ws (r3d_losses_fwd_bwd's layout, r3d_losses_ws_floats(B, S, Q) floats with N = B S) = the segmentation unit
+ *     r3d_losses_fwd_bwd_kseg computes for row r: masked when labels[r] is pad_idx, exclude_idx or outside [0, Kseg), + 2
+ *     when the arg-max (first occurrence of the largest logit) is pad_idx; reduce with has_seg = 1.  Only the N segmentation
+ *     units are written: run it AFTER r3d_afft_head_step on the same ws (which zeroes them and writes the others);
+ *   d_seg [N, Kseg] (row stride ld_dseg) = (softmax(logits) - onehot) grad_scale / N, zero on masked rows;
+ *   d_pre [N, H] = (x > 0) ? d_seg . w + d_x0 + d_extra : 0; d_x0 and d_extra are optional [N, H] with their own row strides.
+ * w [Kseg, H] contiguous.  No atomics; the same call gives the same bits.
+ * r3d_cnn_seg_supported (host-only): H % 4 == 0, 8 <= H <= 256, 1 <= Kseg <= 1023.  A refused shape returns R3D_EINVAL
+ * before anything is enqueued; x, w, d_x0, d_extra, d_pre and ws 16-byte aligned, ld_x, ld_dx0, ld_dextra and ld_dpre
+ * multiples of 4 (R3D_EALIGN). */
+typedef struct r3d_cnn_seg_args {
+    const float* x; int32_t ld_x;
+    const float* w; const float* b;
+    const int64_t* labels;
+    int32_t N, H, Kseg;
+    int32_t pad_idx, exclude_idx; float grad_scale;
+    float* seg; int32_t ld_seg;
+    float* d_seg; int32_t ld_dseg;
+    const float* d_x0; int32_t ld_dx0;
+    const float* d_extra; int32_t ld_dextra;
+    float* d_pre; int32_t ld_dpre;
+} r3d_cnn_seg_args;
+int r3d_cnn_seg_supported(int H, int Kseg);
+int r3d_cnn_seg_step(const r3d_cnn_seg_args* args, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,15 @@ class AfftHeadArgs(C.Structure):
                 ("add", C.c_int32), ("tick_a", C.c_void_p), ("tick_b", C.c_void_p)]
 
 
+class CnnSegArgs(C.Structure):
+    """struct r3d_cnn_seg_args"""
+    _fields_ = [("x", C.c_void_p), ("ld_x", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p), ("labels", C.c_void_p),
+                ("N", C.c_int32), ("H", C.c_int32), ("Kseg", C.c_int32), ("pad_idx", C.c_int32), ("exclude_idx", C.c_int32),
+                ("grad_scale", C.c_float), ("seg", C.c_void_p), ("ld_seg", C.c_int32), ("d_seg", C.c_void_p),
+                ("ld_dseg", C.c_int32), ("d_x0", C.c_void_p), ("ld_dx0", C.c_int32), ("d_extra", C.c_void_p),
+                ("ld_dextra", C.c_int32), ("d_pre", C.c_void_p), ("ld_dpre", C.c_int32)]
+
+
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 
 _I, _L, _F, _P, _D = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_double
@@ -320,6 +329,8 @@ _SIGNATURES = {
     "r3d_afft_head_supported": ([_I, _I, _I], C.c_int),
     "r3d_afft_head_fwd": ([_P, _P], C.c_int),
     "r3d_afft_head_step": ([_P, _P, _P], C.c_int),
+    "r3d_cnn_seg_supported": ([_I, _I], C.c_int),
+    "r3d_cnn_seg_step": ([_P, _P, _P], C.c_int),
     "r3d_focal_rows": ([_P, _I, _P, _I, _I, _L, _I, _L, _F, _F, _F, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P], C.c_int),
 }
 

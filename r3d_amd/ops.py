@@ -1604,3 +1604,40 @@ def afft_head_step(fused, w_head, b_head, pooled, out, B, S, Q, past_label, targ
     a.d_out, a.ld_dout, a.d_fused, a.ld_dfused = d_out.data_ptr(), _ld(d_out), d_fused.data_ptr(), _ld(d_fused)
     a.gscale, a.add, a.tick_a, a.tick_b = gscale, 1 if add else 0, _pv(tick_a), _pv(tick_b)
     check(_lib.load().r3d_afft_head_step(C.byref(a), _p(ws), _stream()), "r3d_afft_head_step")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# CNN baseline: the segmentation-head step (csrc/cnn.hip)
+# ----------------------------------------------------------------------------------------------------------
+def cnn_seg_supported(H, Kseg):
+    return bool(_lib.load().r3d_cnn_seg_supported(H, Kseg))
+
+
+def cnn_seg_step(x, w, b, labels, pad_idx, exclude_idx, d_seg, d_pre, ws, *, seg=None, d_x0=None, d_extra=None, grad_scale=1.0):
+    """One launch over the rows of x [N, H]: logits = x . w^T + b (stored to seg when given), the rows' segmentation units
+    of the loss partials in ws (the layout of losses_fwd_bwd_kseg; run it after afft_head_step on the same ws and reduce with
+    has_seg = True), d_seg [N, Kseg] and d_pre = (x > 0) ? d_seg . w + d_x0 + d_extra : 0."""
+    Kseg, H = w.shape
+    if not cnn_seg_supported(H, Kseg):
+        raise ValueError(f"hidden {H}, {Kseg} segmentation classes: the segmentation-head step takes hidden % 4 == 0, "
+                         f"8 <= hidden <= 256 and 1 <= classes <= 1023")
+    N = x.shape[0]
+    for t in (x, w, b, d_seg, d_pre, ws):
+        _f32(t)
+    assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous() and labels.numel() == N
+    assert N > 0 and x.shape == (N, H) and w.is_contiguous() and b.is_contiguous() and b.numel() == Kseg
+    assert d_seg.shape == (N, Kseg) and d_pre.shape == (N, H) and ws.numel() >= 4 * N
+    a = _lib.CnnSegArgs()
+    a.x, a.ld_x, a.w, a.b, a.labels = x.data_ptr(), _ld(x), w.data_ptr(), b.data_ptr(), labels.data_ptr()
+    a.N, a.H, a.Kseg, a.pad_idx, a.exclude_idx, a.grad_scale = N, H, Kseg, pad_idx, exclude_idx, grad_scale
+    a.d_seg, a.ld_dseg, a.d_pre, a.ld_dpre = d_seg.data_ptr(), _ld(d_seg), d_pre.data_ptr(), _ld(d_pre)
+    if seg is not None:
+        assert _f32(seg).shape == (N, Kseg)
+        a.seg, a.ld_seg = seg.data_ptr(), _ld(seg)
+    if d_x0 is not None:
+        assert _f32(d_x0).shape == (N, H)
+        a.d_x0, a.ld_dx0 = d_x0.data_ptr(), _ld(d_x0)
+    if d_extra is not None:
+        assert _f32(d_extra).shape == (N, H)
+        a.d_extra, a.ld_dextra = d_extra.data_ptr(), _ld(d_extra)
+    check(_lib.load().r3d_cnn_seg_step(C.byref(a), _p(ws), _stream()), "r3d_cnn_seg_step")

@@ -1,7 +1,8 @@
 """Drop-in for the reference's ``train/train_unimodal.py`` (``from train_unimodal import train``, main_nturgbd.py:32):
 ``train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed)``
 and ``validate(model, val_loader, criterion, pad_idx, device)`` with the reference's signatures, skip rules, loss
-composition, prints and checkpoint names, driving the RNN baseline (r3d_amd.model.rnn.FUTR).  Each batch is one replay of
+composition, prints and checkpoint names, driving either unimodal baseline (r3d_amd.model.rnn.FUTR or
+r3d_amd.model.cnn.FUTR; the shape check dispatches on the model, everything else is shared).  Each batch is one replay of
 the fused step (forward + 3 losses + backward + AdamW, train_proposed_depth._GraphedSteps) with no device->host sync;
 epoch statistics are read back once per epoch.
 
@@ -18,7 +19,7 @@ torch.distributed runs are refused (the reference's nn.DataParallel wrapper, mai
 Build-defined addition: ``--supcon_weight W`` (default 0.0: none of the following is launched) adds W * SupConLoss(
 temperature=args.temperature, normalize=True, ignore_index=pad_idx) over the B * S rows of ``outputs['supcon']`` with the
 labels ``past_label.view(-1)`` -- the use main_nturgbd.py:137 prepares and the reference's loop leaves commented out --
-to the step's loss, inside the step (engine_rnn.RnnEngine.losses / backward); the epoch's ``Loss`` includes it and one
+to the step's loss, inside the step (the engine's losses / backward; the CNN model's rows are x, hidden <= 256); the epoch's ``Loss`` includes it and one
 ``supcon loss`` line follows the ``seg loss`` line.  validate() is unchanged.
 """
 import os
@@ -27,18 +28,28 @@ import torch
 import torch.distributed as dist
 
 from .model.rnn import FUTR
+from .model.cnn import FUTR as FUTRCnn
 from .optim import FlatAdamW
 from .engine_rnn import check_rnn_shape
+from .engine_cnn import check_cnn_shape
 from .train_proposed_depth import _GraphedSteps, get_last_non_padding_labels, weighted_accuracy  # noqa: F401
 
 
 def _unwrap(model):
     m = model
-    while hasattr(m, "module") and not isinstance(m, FUTR):
+    while hasattr(m, "module") and not isinstance(m, (FUTR, FUTRCnn)):
         m = m.module
-    if not isinstance(m, FUTR):
-        raise TypeError("r3d_amd.train_unimodal drives r3d_amd.model.rnn.FUTR")
+    if not isinstance(m, (FUTR, FUTRCnn)):
+        raise TypeError("r3d_amd.train_unimodal drives r3d_amd.model.rnn.FUTR or r3d_amd.model.cnn.FUTR")
     return m
+
+
+def _check_shape(core, erank_weight):
+    """The model's own admission rule, on the host, before anything is enqueued."""
+    if isinstance(core, FUTRCnn):
+        check_cnn_shape(core.hidden_dim, core.n_query, core.n_class, erank_weight, input_dim=core.input_embed.in_features)
+    else:
+        check_rnn_shape(core.hidden_dim, core.n_query, erank_weight)
 
 
 def _to_dev(data, device):
@@ -106,9 +117,9 @@ def validate(model, val_loader, criterion, pad_idx, device):
 
 def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
     core = _unwrap(model)
-    check_rnn_shape(core.hidden_dim, core.n_query, float(getattr(args, "erank_weight", 0.0) or 0.0))
+    _check_shape(core, float(getattr(args, "erank_weight", 0.0) or 0.0))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise NotImplementedError("r3d_amd.train_unimodal trains the RNN model on one GPU; multi-rank torch.distributed "
+        raise NotImplementedError("r3d_amd.train_unimodal trains its model on one GPU; multi-rank torch.distributed "
                                   "runs of it are not supported")
     model.to(device)
     model.train()
