@@ -941,6 +941,39 @@ typedef struct r3d_cnn_seg_args {
 int r3d_cnn_seg_supported(int H, int Kseg);
 int r3d_cnn_seg_step(const r3d_cnn_seg_args* args, float* ws, void* stream);
 
+/* ---- L3 query model: cross-clip attention (csrc/attention_xclip.hip; model/futr_unsupervised_temp3.py:99-102) --------------
+ * nn.MultiheadAttention(batch_first=True) called after 'b t c -> t b c': for each frame t and head h the B rows { b S + t }
+ * attend to one another, no mask, no dropout.  qkv [B S, 3 H] (row stride ld >= 3 H, H = heads dh) is the in-projection
+ * output, columns [q | k | v], head h at columns h dh of each part; it is read in place (the keys of one group lie S ld
+ * floats apart), no transposed copy is made.
+ * r3d_xclip_fwd: o [B S, H] (row stride ldo) = softmax(q k^T / sqrt(dh)) v per (t, h).
+ * r3d_xclip_bwd: d_qkv [B S, 3 H] (row stride lddq), every element written once (not accumulated), from qkv and d_o [B S, H]
+ *   (row stride lddo); the probabilities are recomputed.
+ * Each launch enqueues only; no atomics, fixed-order sums (the same call gives the same bits).  16-byte loads are used where
+ * the pointers, row strides and column offsets are multiples of 4 floats; any alignment runs.
+ * r3d_xclip_supported (host-only): 1 <= B <= 64, 1 <= dh <= 128; also S >= 1 and B S 3 H < 2^31.  A refused shape returns
+ *   R3D_EINVAL before anything is enqueued.
+ * r3d_xclip_frame_run (host-only): the consecutive frames one workgroup owns at that shape (0: refused). */
+int r3d_xclip_supported(int B, int dh);
+int r3d_xclip_frame_run(int B, int S, int heads, int dh, int bwd);
+int r3d_xclip_fwd(const float* qkv, int ld, float* o, int ldo, int B, int S, int heads, int dh, void* stream);
+int r3d_xclip_bwd(const float* qkv, int ld, const float* d_o, int lddo, float* d_qkv, int lddq, int B, int S, int heads,
+                  int dh, void* stream);
+
+/* ---- L3 query loop: the loss mix (csrc/l3mix.hip; train/train_unsupervised.py:357-362) -------------------------------------
+ * Over the N = B S frame rows: l2_correct[r] = [past_label[r] != pad_idx and argmax(seg[r]) == past_label[r]] (the first
+ * index of the maximum; seg [N, Kseg], row stride ld_seg), l3_flags the flags of r3d_focal_rows,
+ *   m = mean_r (l3_flags[r] && l2_correct[r] ? 1 : 5),  c = 1/m,  a = (1 - c)(1 - wf),  b = (1 - c) wf,
+ *   total = (1 - c)((1 - wf) l3[0] + wf lc[0]) + c ((loss3[1] + loss3[2]) + loss3[0]),
+ * loss3 = the loss_out of r3d_losses_fwd_bwd (seg, action, duration); l3, lc, wf device scalars.  Writes out[5] = (m, a, b,
+ * c, total), l2_flags uint8 [N] when not NULL, and multiplies d_seg [N, Kseg] (row stride ld_dseg) and d_actdur [rows_ad,
+ * cols_ad] (row stride ld_dad) by c in place (either may be NULL).  ws: r3d_l3mix_ws_ints(N) int32 of scratch.  Two launches,
+ * enqueue only; the count behind m is an integer sum: no float atomics, the same call gives the same bits. */
+int64_t r3d_l3mix_ws_ints(int N);
+int r3d_l3mix(const float* seg, int ld_seg, const int64_t* past_label, const uint8_t* l3_flags, int N, int Kseg, int pad_idx,
+              const float* l3, const float* lc, const float* loss3, const float* wf, float* d_seg, int ld_dseg,
+              float* d_actdur, int rows_ad, int cols_ad, int ld_dad, uint8_t* l2_flags, int* ws, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

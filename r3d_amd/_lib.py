@@ -332,6 +332,12 @@ _SIGNATURES = {
     "r3d_cnn_seg_supported": ([_I, _I], C.c_int),
     "r3d_cnn_seg_step": ([_P, _P, _P], C.c_int),
     "r3d_focal_rows": ([_P, _I, _P, _I, _I, _L, _I, _L, _F, _F, _F, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P], C.c_int),
+    "r3d_xclip_supported": ([_I, _I], C.c_int),
+    "r3d_xclip_frame_run": ([_I, _I, _I, _I, _I], C.c_int),
+    "r3d_xclip_fwd": ([_P, _I, _P, _I, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_xclip_bwd": ([_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_l3mix_ws_ints": ([_I], C.c_int64),
+    "r3d_l3mix": ([_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P], C.c_int),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1641,3 +1641,74 @@ def cnn_seg_step(x, w, b, labels, pad_idx, exclude_idx, d_seg, d_pre, ws, *, seg
         assert _f32(d_extra).shape == (N, H)
         a.d_extra, a.ld_dextra = d_extra.data_ptr(), _ld(d_extra)
     check(_lib.load().r3d_cnn_seg_step(C.byref(a), _p(ws), _stream()), "r3d_cnn_seg_step")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# L3 query model: cross-clip attention (csrc/attention_xclip.hip) and the loss mix (csrc/l3mix.hip)
+# ----------------------------------------------------------------------------------------------------------
+def xclip_supported(B, dh):
+    """The cross-clip attention runs B clips at head width dh: 1 <= B <= 64, 1 <= dh <= 128 (host-only)."""
+    return bool(_lib.load().r3d_xclip_supported(int(B), int(dh)))
+
+
+def xclip_frame_run(B, S, heads, dh, bwd):
+    """The consecutive frames one workgroup of xclip_fwd / xclip_bwd owns at that shape (host-only)."""
+    return int(_lib.load().r3d_xclip_frame_run(int(B), int(S), int(heads), int(dh), 1 if bwd else 0))
+
+
+def _xclip_check(qkv, B, S, heads):
+    N, W = qkv.shape
+    H = W // 3
+    if N != B * S or W != 3 * H or H % heads:
+        raise ValueError(f"qkv {tuple(qkv.shape)}: expected [{B} * {S}, 3 * hidden] with hidden a multiple of {heads} heads")
+    dh = H // heads
+    if not xclip_supported(B, dh):
+        raise ValueError(f"{B} clips at head width {dh}: the cross-clip attention takes 1 <= clips <= 64 and head width <= 128")
+    if B * S * 3 * H >= 2 ** 31:
+        raise ValueError(f"{B} clips of {S} frames at hidden {H}: the cross-clip attention takes B * S * 3 * hidden < 2^31")
+    return H, dh
+
+
+def xclip_fwd(qkv, o, B, S, heads):
+    """o [B S, H] = the attention of each frame's B rows { b S + t } to one another, per head, from the in-projection
+    output qkv [B S, 3 H] read in place (any row stride); one launch, enqueue only."""
+    H, dh = _xclip_check(qkv, B, S, heads)
+    assert o.shape == (B * S, H)
+    check(_lib.load().r3d_xclip_fwd(_p(_f32(qkv, "qkv")), _ld(qkv), _p(_f32(o, "o")), _ld(o), B, S, heads, dh, _stream()),
+          "r3d_xclip_fwd")
+
+
+def xclip_bwd(qkv, d_o, d_qkv, B, S, heads):
+    """d_qkv [B S, 3 H], written in full (not accumulated), from qkv and d_o [B S, H]; the probabilities are recomputed."""
+    H, dh = _xclip_check(qkv, B, S, heads)
+    assert d_o.shape == (B * S, H) and d_qkv.shape == (B * S, 3 * H)
+    check(_lib.load().r3d_xclip_bwd(_p(_f32(qkv, "qkv")), _ld(qkv), _p(_f32(d_o, "d_o")), _ld(d_o), _p(_f32(d_qkv, "d_qkv")),
+                                    _ld(d_qkv), B, S, heads, dh, _stream()), "r3d_xclip_bwd")
+
+
+def l3mix_ws_ints(N):
+    return int(_lib.load().r3d_l3mix_ws_ints(int(N)))
+
+
+def l3mix(seg, past_label, l3_flags, pad_idx, l3, lc, loss3, wf, ws, out, *, d_seg=None, d_actdur=None, l2_flags=None):
+    """The loss mix of the L3 query loop over the rows of seg [N, Kseg]: out[5] = (m, a, b, c, total) with m the mean of
+    (l3_flags & l2_correct ? 1 : 5), c = 1 / m, a = (1 - c)(1 - wf), b = (1 - c) wf and total = (1 - c)((1 - wf) l3 + wf lc)
+    + c (loss3[1] + loss3[2] + loss3[0]); d_seg and d_actdur are multiplied by c in place.  l3, lc, wf: device scalars;
+    loss3: the loss_out of losses_fwd_bwd; ws: l3mix_ws_ints(N) int32.  Two launches, no read-back."""
+    N, Kseg = seg.shape
+    assert past_label.dtype == torch.int64 and past_label.is_cuda and past_label.is_contiguous() and past_label.numel() == N
+    assert l3_flags.is_cuda and l3_flags.element_size() == 1 and l3_flags.is_contiguous() and l3_flags.numel() == N
+    assert ws.dtype == torch.int32 and ws.is_cuda and ws.is_contiguous() and ws.numel() >= l3mix_ws_ints(N)
+    assert _f32(out, "out").is_contiguous() and out.numel() >= 5 and _f32(loss3, "loss3").is_contiguous() and loss3.numel() >= 3
+    for t in (l3, lc, wf):
+        assert _f32(t).numel() >= 1
+    if l2_flags is not None:
+        assert l2_flags.is_cuda and l2_flags.element_size() == 1 and l2_flags.is_contiguous() and l2_flags.numel() == N
+    if d_seg is not None:
+        assert _f32(d_seg, "d_seg").shape == (N, Kseg)
+    ra, ca = d_actdur.shape if d_actdur is not None else (0, 0)
+    check(_lib.load().r3d_l3mix(_p(_f32(seg, "seg")), _ld(seg), _p(past_label), _p(l3_flags), N, Kseg, int(pad_idx), _p(l3),
+                                _p(lc), _p(loss3), _p(wf), _p(d_seg), _ld(d_seg) if d_seg is not None else 0,
+                                _p(None if d_actdur is None else _f32(d_actdur, "d_actdur")), ra, ca,
+                                _ld(d_actdur) if d_actdur is not None else 0, _p(l2_flags), _p(ws), _p(out), _stream()),
+          "r3d_l3mix")
