@@ -675,6 +675,10 @@ int r3d_scale_rows_into(const float* x, int ldx, float* y, int ldy, int rows, in
 int r3d_erank_bwd_coef2(const float* sigma, const float* stats, const float* gout, float* cg, float* inv, int C, int max_rank,
                         void* stream);
 int r3d_erank_bwd_fix(float* w, const float* p, const float* cg, int rows, int cols, void* stream);
+/* The tall rank route's basis clean-up: out [C, C] = I + L, L[i, j] = g2[i, j] / sigma_j^2 where sigma_j > sigma_i (ties:
+ * j < i), 0 elsewhere; g2 = (R V)^T (R V).  V^T <- 2 V^T - (I + L) V^T takes out of every right singular vector its
+ * component along the vectors of larger singular values (first order). */
+int r3d_erank_deflate_mask(const float* g2, const float* sigma, float* out, int C, void* stream);
 /* r3d_erank_jacobi that also carries the right singular basis (batch == 1): every rotation is applied to the rows of
  * V^T as well, vt_out [C][C] = (V0 V')^T.  vt_in = V0^T from an earlier decomposition of a nearby matrix and x = X V0
  * (NULL: identity): a warm start, 3-5 sweeps instead of 10-11.  Matrix and basis must fit the LDS together
@@ -805,6 +809,18 @@ int r3d_qr_append_tile_rows(int H);
 int r3d_qr_append(const float* x, int64_t ldx, int n, int H, const int64_t* row_label, int pad_idx, float* R, int64_t* rows,
                   int lanes, void* stream);
 int r3d_qr_merge(float* R, int64_t* rows, int H, int lanes, int stride, void* stream);
+
+/* ---- blocked fold into the same accumulators (qr_fold_wy.hip): the in-step rank penalty on tall token matrices ----------
+ * r3d_qr_append's contract without labels (every row counts, nothing is counted), computed panel by panel in the
+ * compact-WY form: 16 columns are factored with the reflector formula, everything right of them is updated by fp32-input
+ * MFMA products.  The result is upper triangular with R^T R = sum X^T X (diagonal signs free, not the bits of
+ * r3d_qr_append) and feeds r3d_qr_merge.  Fixed-order sums, no atomics: the same call gives the same bits.
+ * r3d_qr_fold_wy_supported: H a multiple of 16 whose LDS tile keeps at least 32 rows next to 16 staged rows of R
+ *   (16 <= H <= 720).  r3d_qr_fold_wy_tile_rows: the rows of one tile at width H (a multiple of 16; 0: refused).
+ * r3d_qr_fold_wy: n = 0 is a no-op; 1 <= lanes <= 64; ldx >= H; a refused H is R3D_EINVAL before any launch. */
+int r3d_qr_fold_wy_supported(int H);
+int r3d_qr_fold_wy_tile_rows(int H);
+int r3d_qr_fold_wy(const float* x, int64_t ldx, int n, int H, float* R, int lanes, void* stream);
 
 /* ---- supervised contrastive loss (supcon.hip; reference loss/spc.py SupConLoss) -----------------------------------------
  * x [N, D] fp32 (row stride ldx >= D): the contrast rows, view by view; row r carries labels[r mod bsz] (int64 [bsz];

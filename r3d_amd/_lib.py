@@ -282,6 +282,7 @@ _SIGNATURES = {
     "r3d_erank_bwd_coef": ([_P, _P, _P, _P, _I, _I, _P], C.c_int),
     "r3d_erank_bwd_coef2": ([_P, _P, _P, _P, _P, _I, _I, _P], C.c_int),
     "r3d_erank_bwd_fix": ([_P, _P, _P, _I, _I, _P], C.c_int),
+    "r3d_erank_deflate_mask": ([_P, _P, _P, _I, _P], C.c_int),
     "r3d_scale_rows": ([_P, _I, _I, _I, _P, _P], C.c_int),
     "r3d_scale_rows_into": ([_P, _I, _P, _I, _I, _I, _P, _P], C.c_int),
     "r3d_posenc_fwd": ([_P, _I, _P, _I, _I, _P, _F, _P, _I, _I, _I, _P], C.c_int),
@@ -314,6 +315,9 @@ _SIGNATURES = {
     "r3d_qr_append_tile_rows": ([_I], C.c_int),
     "r3d_qr_append": ([_P, _L, _I, _I, _P, _I, _P, _P, _I, _P], C.c_int),
     "r3d_qr_merge": ([_P, _P, _I, _I, _I, _P], C.c_int),
+    "r3d_qr_fold_wy_supported": ([_I], C.c_int),
+    "r3d_qr_fold_wy_tile_rows": ([_I], C.c_int),
+    "r3d_qr_fold_wy": ([_P, _L, _I, _I, _P, _I, _P], C.c_int),
     "r3d_supcon_supported": ([_I], C.c_int),
     "r3d_supcon_ws_floats": ([_I], C.c_int64),
     "r3d_supcon_fwd": ([_P, _I, _P, _I, _I, _I, _I, _I, _L, _F, _F, _I, _P, _P, _P], C.c_int),

@@ -653,6 +653,21 @@ __global__ __launch_bounds__(256) void erank_bwd_fix_kernel(float* w, const floa
         w[e] = cg[e / cols] * (2.f * w[e] - p[e]);
 }
 
+// out = I + L, L[i, j] = g2[i, j] / sigma_j^2 where column j comes before i in descending-sigma order (ties: the lower
+// index), 0 elsewhere: one first-order step of Gram-Schmidt in the R^T R inner product, larger singular values first
+// (r3d_erank_deflate_mask)
+__global__ __launch_bounds__(256) void erank_deflate_mask_kernel(const float* __restrict__ g2, const float* __restrict__ sigma,
+                                                                 float* __restrict__ out, int C) {
+    const size_t total = (size_t)C * C;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const int i = (int)(e / C), j = (int)(e % C);
+        const float si = sigma[i], sj = sigma[j];
+        float v = i == j ? 1.f : 0.f;
+        if (i != j && sj > 0.f && (sj > si || (sj == si && j < i))) v = g2[e] / (sj * sj);
+        out[e] = v;
+    }
+}
+
 // y[r, c] = x[r, c] * coef[r]  (y == x: in place)
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* x, int ldx, float* y, int ldy, int rows, int cols,
                                                          const float* coef) {
@@ -973,6 +988,16 @@ R3D_EXPORT int r3d_erank_bwd_fix(float* w, const float* p, const float* cg, int 
     const size_t total = (size_t)rows * cols;
     const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
     hipLaunchKernelGGL(erank_bwd_fix_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, p, cg, rows, cols);
+    R3D_LAUNCH_CHECK();
+    return R3D_OK;
+}
+
+/* out [C, C] = I + L with L[i, j] = g2[i, j] / sigma_j^2 where sigma_j > sigma_i (ties: j < i), else 0; g2, out dense. */
+R3D_EXPORT int r3d_erank_deflate_mask(const float* g2, const float* sigma, float* out, int C, void* stream) {
+    R3D_REQUIRE(g2 && sigma && out && g2 != out && C > 0);
+    const size_t total = (size_t)C * C;
+    const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+    hipLaunchKernelGGL(erank_deflate_mask_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g2, sigma, out, C);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
 }

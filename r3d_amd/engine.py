@@ -99,14 +99,27 @@ def check_clip_shape(S, H, heads, Q, max_pos_len, train):
                          f"keeps {Q} x {S} scores in LDS, past its 160 KiB")
 
 
-def check_erank_shape(B, S, H):
-    """Raises ValueError unless the rank penalty's Jacobi runs on the [B*S, H] fused tokens: in one CU's LDS, or blocked
-    on the orientation with the fewer columns (columns of max(B*S, H) rows, two blocks of them in LDS)."""
+ERANK_ROUTES = ("jacobi", "tall")
+
+
+def check_erank_shape(B, S, H, route="jacobi"):
+    """Raises ValueError unless the rank penalty runs on the [B*S, H] fused tokens.  route "jacobi": the Jacobi in one CU's
+    LDS, or blocked on the orientation with the fewer columns (columns of max(B*S, H) rows, two blocks of them in LDS).
+    route "tall" (erank.ErankTall: the rows are QR-reduced to [H, H] first): N >= H, H <= 2048, N * H < 2^31."""
     N = B * S
+    if route == "tall":
+        from .erank import check_tall_shape
+        try:
+            check_tall_shape(N, H)
+        except ValueError as e:
+            raise ValueError(f"{B} clips x {S} frames at hidden {H} with the rank penalty: {e}") from None
+        return
+    if route != "jacobi":
+        raise ValueError(f"erank_route {route!r}: one of {ERANK_ROUTES}")
     if ops.erank_fits(N, H) or ops.erank_blocked_supported(max(N, H), min(N, H)):
         return
     raise ValueError(f"{B} clips x {S} frames at hidden {H} with the rank penalty: the blocked Jacobi holds two blocks of "
-                     f"{max(N, H)}-long columns in LDS, past its 150 KiB")
+                     f"{max(N, H)}-long columns in LDS, past its 150 KiB (--erank_route tall admits it)")
 
 
 def max_clip_len(H, heads, Q, max_pos_len, train):
@@ -391,6 +404,17 @@ class FusionEngine:
         # at lr 1e-3 from a random init the tokens move 20-100 % per step and no basis survives (measured: 1.54 vs
         # 1.27 ms/step at the headline shape), so it is opt-in
         self.erank_warm_start = False
+        # "jacobi": the sweep on the [N, H] tokens themselves (N <= 9596).  "tall": erank.ErankTall -- the rows are folded
+        # into an [H, H] triangle first (any N >= H); erank_warm_start is ignored there (the sweep runs on R, whose basis is
+        # not carried between steps).  One GPU only: the data-parallel and pixel-sharded engines refuse "tall".
+        # On the tall route the sweep decomposes [2H, H]: in one CU's LDS up to H = 128 (30 sweeps enqueued, as the op), the
+        # blocked kernel from H = 256 on with erank_max_sweeps enqueued, as on the Jacobi route -- a spectrum that needs more
+        # (clusters 0.1 % apart at sigma_max / sigma_min = 1e4 took 18 at [2048, 256]) leaves an unconverged sweep and a
+        # gradient that is off without an error; raise erank_max_sweeps for such data (stats[3] is the sweeps used).
+        self.erank_route = "jacobi"
+        # tall route: "wy" | "column" | None (erank.fold_pays).  Part of train()'s graph key; a loop of its own sets it
+        # before the first step (a change rebuilds the route's buffers on the next forward, which must not be a replay)
+        self.erank_fold = None
         self.erank_max_sweeps = 16        # blocked (two-level) Jacobi: sweeps enqueued per step (8-10 are used; the rest no-op)
         # the Jacobi forward depends on the fused tokens only: it is enqueued on a second stream as soon as they exist (a
         # parallel branch of the step's hipGraph) and joined where its backward adds into the fuser's upstream gradient --
@@ -476,7 +500,10 @@ class FusionEngine:
         assert x_rgb.shape[1] == self.D and x_dep.shape[1] == self.P, (x_rgb.shape, x_dep.shape, self.D, self.P)
         assert x_rgb.is_contiguous() and x_dep.is_contiguous()
         if need_grad and self.erank_weight != 0.0:
-            check_erank_shape(B, S, self.H)      # (before anything is enqueued, as _shape's own checks)
+            if self.erank_route == "tall" and (self.tp is not None or self.grad_hook is not None):
+                raise ValueError("erank_route 'tall' on a data-parallel or pixel-sharded engine: the tall rank route runs "
+                                 "on one GPU; use erank_route 'jacobi'")
+            check_erank_shape(B, S, self.H, self.erank_route)      # (before anything is enqueued, as _shape's own checks)
         w = self._shape(B, S, need_grad)
         self._loss_pending = None          # (see losses(): a pending loss reduction never survives into another step)
         self._erank_join()                 # (a forward whose backward never ran: its sweep still reads the workspace)
@@ -751,6 +778,14 @@ class FusionEngine:
         sweeps replace 10-11.  The singular values of X V0 are those of X (V0 orthogonal), and the rotated columns
         Af = X V0 V' are the same (X V) the backward needs."""
         N, H = w.N, self.H
+        if self.erank_route == "tall":
+            if getattr(w, "er_tall", None) is None or w.er_tall.fold != self._tall_fold(N, H):
+                from .erank import ErankTall
+                w.er_tall = ErankTall(N, H, self.device, fold=self.erank_fold, max_sweeps=30 if ops.erank_fits(2 * H, H)
+                                      else self.erank_max_sweeps)
+                w.er_tall_gout = torch.empty(1, dtype=torch.float32, device=self.device)
+            w.er_tall.forward(w.fused)
+            return
         if not hasattr(w, "er_sigma"):
             f = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)     # noqa: E731
             w.er_gout = f(1)
@@ -785,6 +820,10 @@ class FusionEngine:
         """d_fused2 += d(-erank_weight * erank)/d(fused)  (dst given: dst = that gradient, written, not accumulated): U diag(g)
         V^T from the rotated columns the sweep left behind, in the Neumann-corrected form of r3d_amd.erank.ErankBackward;
         when the sweep ran on fused^T (wide token matrices) the same products in the transposed orientation."""
+        if self.erank_route == "tall":
+            w.er_tall_gout.fill_(-float(self.erank_weight))
+            w.er_tall.backward(w.fused, w.er_tall_gout, dst if dst is not None else w.d_fused2, dst is None, ws)
+            return
         from .erank import ErankBackward
         if not hasattr(w, "er_bwd"):
             w.er_bwd = ErankBackward(w.N, self.H, w.er_blk is not None and w.er_flip, self.device,
@@ -797,7 +836,12 @@ class FusionEngine:
     def erank_value(self):
         """Effective rank of the last forward's fused tokens (device scalar; valid when erank_weight != 0)."""
         self._erank_join()
-        return self.last["w"].er_stats[0, 0]
+        w = self.last["w"]
+        return w.er_tall.stats[0, 0] if self.erank_route == "tall" else w.er_stats[0, 0]
+
+    def _tall_fold(self, N, H):
+        from .erank import fold_pays
+        return self.erank_fold if self.erank_fold is not None else fold_pays(N, H)
 
     def chain_planes(self):
         """The bf16x3 planes of the chain kernels' weights (built on first use; refresh() re-splits the current parameters)."""

@@ -1114,6 +1114,13 @@ def erank_bwd_fix(w, p, cg):
     check(_lib.load().r3d_erank_bwd_fix(_p(w), _p(p), _p(cg), w.shape[0], w.shape[1], _stream()), "r3d_erank_bwd_fix")
 
 
+def erank_deflate_mask(g2, sigma, out):
+    """out = I + L, L[i, j] = g2[i, j] / sigma_j^2 where sigma_j > sigma_i (ties: j < i), else 0 (r3d_erank_deflate_mask)."""
+    Cc = sigma.numel()
+    assert g2.is_contiguous() and out.is_contiguous() and tuple(g2.shape) == tuple(out.shape) == (Cc, Cc)
+    check(_lib.load().r3d_erank_deflate_mask(_p(g2), _p(sigma), _p(out), Cc, _stream()), "r3d_erank_deflate_mask")
+
+
 def scale_rows(x, coef):
     lib = _lib.load()
     rows, cols = x.shape
@@ -1187,6 +1194,30 @@ def qr_append(x, R, *, rows=None, row_label=None, pad_idx=0):
                                       and row_label.numel() == n), f"row_label must be a contiguous int64 device tensor [{n}]")
     check(_lib.load().r3d_qr_append(_p(x) if n > 0 else None, ldx, n, H, _p(row_label), int(pad_idx), _p(R), _p(rows), lanes,
                                     _stream()), "r3d_qr_append")
+
+
+def qr_fold_wy_supported(H):
+    """r3d_qr_fold_wy takes rows of width H (host only): multiples of 16 up to the LDS budget."""
+    return bool(_lib.load().r3d_qr_fold_wy_supported(H))
+
+
+def qr_fold_wy_tile_rows(H):
+    """Rows of one LDS tile of r3d_qr_fold_wy at width H (host only; 0 when H is refused)."""
+    return int(_lib.load().r3d_qr_fold_wy_tile_rows(H))
+
+
+def qr_fold_wy(x, R):
+    """qr_append without labels through the blocked compact-WY kernel (qr_fold_wy.hip): folds every row of x [n, H] into
+    R [lanes, H, H].  Enqueue only.  A malformed tensor raises ValueError, a refused H / lanes / ldx R3DHipError
+    (R3D_EINVAL), both before any launch."""
+    lanes, H = _qr_accumulators(R, None)
+    _qr_require(x.dim() == 2 and x.shape[1] == H, f"x must be [n, {H}], got {tuple(x.shape)}")
+    n = x.shape[0]
+    if n > 0:
+        _qr_require(x.dtype == torch.float32 and x.is_cuda, "x must be a float32 device tensor")
+        _qr_require(x.stride(1) == 1 or H == 1, "x needs unit column stride")
+    ldx = x.stride(0) if n > 1 else max(x.stride(0), H)
+    check(_lib.load().r3d_qr_fold_wy(_p(x) if n > 0 else None, ldx, n, H, _p(R), lanes, _stream()), "r3d_qr_fold_wy")
 
 
 def qr_merge(R, rows=None):

@@ -52,6 +52,10 @@ parser.add_argument("--erank_every", type=int, default=0,
 parser.add_argument("--erank_weight", type=float, default=0.0,
                     help="rank-enhancing penalty: total loss -= erank_weight * effective_rank(fused tokens) "
                          "(0 = the reference's loss; the reference describes the quantity, README.md:8-14, but never computes it)")
+parser.add_argument("--erank_route", choices=("jacobi", "tall"), default="jacobi",
+                    help="how the rank penalty decomposes the fused tokens [batch * frames, hidden]: jacobi = the sweep on the "
+                         "tokens themselves (at most 9596 rows); tall = rows QR-reduced to [hidden, hidden] first, then the "
+                         "sweep (any batch with batch * frames >= hidden; one GPU)")
 parser.add_argument("--no_graph_steps", dest="graph_steps", action="store_false", default=True,
                     help="enqueue every training step launch by launch instead of replaying it as a hipGraph (one GPU)")
 parser.add_argument("--restore_train_mode", action="store_true", default=False,

@@ -38,12 +38,19 @@ def shard_range(n_items, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def refuse_tall_route(engine, who):
+    """The tall rank route (engine.erank_route = "tall") has only been run on one GPU: not offered under `who`."""
+    if getattr(engine, "erank_route", "jacobi") == "tall":
+        raise ValueError(f"erank_route 'tall' with {who}: the tall rank route runs on one GPU; use erank_route 'jacobi'")
+
+
 class PixelShardedDepth:
     """depth_projection (futr_safuser_tokenfusion.py:143,194-195) tensor-parallel over its 50176 input pixels."""
 
     def __init__(self, engine, process_group=None, equal_batches=True, input_group=None):
         """input_group: a second communicator for the input all-to-all, so that a prefetch does not queue ahead of the
         step's own (latency-critical) exchanges on the gradient communicator's stream."""
+        refuse_tall_route(engine, "a pixel-sharded depth projection")
         self.eng, self.pg = engine, process_group
         self.pg_in = input_group if input_group is not None else process_group
         self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
@@ -250,6 +257,7 @@ class DataParallelStep:
                  sync_bn=True):
         """sync_bn (BN-blend variant only): batch statistics over the GLOBAL batch, as the single-process reference sees it
         (False = per-rank statistics, what nn.DataParallel gives the reference)."""
+        refuse_tall_route(engine, "a data-parallel step")
         self.eng = engine
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
@@ -388,6 +396,7 @@ class RcclStep:
 
     def __init__(self, dp, comm, comm_side, lr, weight_decay, fuse_adam=False):
         self.dp, self.eng, self.tp = dp, dp.eng, dp.tp
+        refuse_tall_route(self.eng, "the RCCL step")
         if getattr(self.eng, "vary", False):
             raise NotImplementedError("the activation-magnitude fuser variant (futr_safuser_tokenfusion_vary) all-reduces "
                                       "its selection scores through torch.distributed inside the step; no one-graph RCCL step")
@@ -428,6 +437,7 @@ class RcclStep:
         step starts cannot stage it a step ahead); lr / hyper = (weight_decay, betas, eps): override the constructor's;
         after_losses(loss, counts): called where the loss kernel's outputs exist (epoch accumulators)."""
         eng, dp, tp = self.eng, self.dp, self.tp
+        refuse_tall_route(eng, "the RCCL step")
         hook, eng.grad_hook = eng.grad_hook, None
         dp.comm_override = self.comm
         keep_defer, eng.defer_tail = eng.defer_tail, True     # forward -> losses -> backward back to back

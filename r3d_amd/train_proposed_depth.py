@@ -83,7 +83,9 @@ class _GraphedSteps:
 
     def step(self, batch, lr, hyper, training):
         eng = self.eng
-        key = tuple(tuple(t.shape) for t in batch) + (bool(training), float(eng.erank_weight))
+        key = tuple(tuple(t.shape) for t in batch) + (bool(training), float(eng.erank_weight),
+                                                      str(getattr(eng, "erank_route", "jacobi")),
+                                                      str(getattr(eng, "erank_fold", None)))
         st = self.shapes.get(key)
         if st is None:
             st = self.shapes[key] = dict(buf=[torch.empty_like(t) for t in batch], seen=0, graph=None, hyper=None)
@@ -349,6 +351,15 @@ def validate(model, val_loader, criterion, pad_idx, device):
     return val_loss, val_accuracy, val_weighted_accuracy
 
 
+def _print_erank(eng):
+    """--erank_every's line.  The measurement takes the penalty's route where it admits the tokens: past 9596 rows only the
+    tall one decomposes them."""
+    from .erank import effective_rank
+    fused = eng.last["w"].fused
+    tall = getattr(eng, "erank_route", "jacobi") == "tall" and fused.shape[0] >= fused.shape[1]
+    print("effective rank of fused tokens: %.3f" % float(effective_rank(fused, route="tall" if tall else "auto")))
+
+
 def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
     refuse_supcon_weight(args, "train_proposed_depth")
     core = _unwrap(model)
@@ -360,6 +371,8 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     dp = None
     parallel = dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1
                                                                   or os.environ.get("R3D_REHEARSE_DIST") == "1")
+    if getattr(args, "erank_route", "jacobi") == "tall" and parallel:
+        raise ValueError("--erank_route tall under data parallelism: the tall rank route runs on one GPU")
     if getattr(args, "erank_report", False) and parallel:
         raise ValueError("--erank_report under data parallelism: each rank validates a shard and the streaming QR's R is "
                          "not merged across ranks; run the report on one GPU")
@@ -378,6 +391,8 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         rank_accs = rankstream.attach(core)          # (ValueError for the query models: no fused token matrix)
         rankstream.detach(core)                      # fed by validate()'s forwards only
     eng.erank_weight = float(getattr(args, "erank_weight", 0.0))
+    if hasattr(eng, "erank_route"):      # (the engines without a fused token matrix refuse the penalty itself)
+        eng.erank_route = str(getattr(args, "erank_route", "jacobi"))
     print("Training Start")
     best_val_loss = float("inf")
     best_val_acc = 0
@@ -452,8 +467,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
                              (g["weight_decay"], tuple(g["betas"]), g["eps"]), model.training)
                 n_steps += 1
                 if erank_every and n_steps % erank_every == 0:
-                    from .erank import effective_rank
-                    print("effective rank of fused tokens: %.3f" % float(effective_rank(eng.last["w"].fused)))
+                    _print_erank(eng)
                 continue
             if dp is not None:
                 dp.prepare_duration_denominator(trans_dur_future, pad_idx)
@@ -480,8 +494,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
             acc_cnt += counts
             n_steps += 1
             if erank_every and n_steps % erank_every == 0:
-                from .erank import effective_rank
-                print("effective rank of fused tokens: %.3f" % float(effective_rank(eng.last["w"].fused)))
+                _print_erank(eng)
         lsum, csum = acc_loss.cpu(), acc_cnt.cpu()                  # the single device->host read of the epoch
         denom = i + 1                                                # the reference divides by (i+1), skipped or not (:218)
         epoch_loss = float(lsum[3]) / denom if denom else 0.0
