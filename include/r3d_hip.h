@@ -450,6 +450,32 @@ int r3d_embed_fuse_bwd(const float* d_h1, const float* x0, const float* m1, cons
                        const float* mask_rgb, const float* mask_dep, const float* rgb, const float* dep_pre,
                        const float* mean_d, const float* rstd_d, const float* lnd_gamma, const float* lnd_beta,
                        float* d_rgb_pre, float* d_dep_pre, float* ws_n1, float* ws_dep, int N, int H, void* stream);
+/* ---- the same seam for THREE modalities (build-defined, as r3d_token_exchange3_*: model/futr_safuser_tokenfusion3.py) ----
+ * r3d_embed_fuse3_fwd : the slab conventions of r3d_embed_fuse_fwd for rgb_src / dep_src; the third embedding is
+ *                       gz = relu(LN_g(b_gaze + w_gaze . gaze[n])) with gaze [N][gaze_dim], w_gaze [H][gaze_dim],
+ *                       1 <= gaze_dim <= 8.  mask [3][H] (1.0 / 0.0): token m takes its masked columns from modality
+ *                       (m + 1) mod 3; drop_mask (optional) [3N][H].  x0 / h1 [3N][H] and m1 / r1 [3N], rows frame-major
+ *                       (3n + m); rgb_out, dep_pre_out, dep_out, gz_pre_out, gz_out [N][H]; mean_* / rstd_* [N].
+ * r3d_embed_fuse3_bwd : norm1 backward (+ add1, add2), dropout, exchange adjoint, the RGB ReLU and both LayerNorm + ReLU
+ *                       adjoints -> d_rgb_pre, d_dep_pre, d_gz_pre [N][H]; ws_n1 / ws_dep / ws_gz [N][2][H] per-frame
+ *                       (dgamma, dbeta) partials (r3d_layernorm_bwd_finalize_batched job with rows = -N).
+ *                       (d gaze_projection = d_gz_pre^T . gaze with its column sums is an r3d_gemm_f32 TN product with
+ *                       bias_grad: its scalar path takes an output gaze_dim wide.)
+ * No atomics: the same call gives the same bits.  All matrices contiguous, ld = H <= 1024. */
+int r3d_embed_fuse3_fwd(const float* rgb_src, int ns_r, const float* bias_r, const float* dep_src, int ns_d,
+                        const float* bias_d, const float* lnd_gamma, const float* lnd_beta, const float* gaze,
+                        const float* w_gaze, const float* b_gaze, const float* lng_gamma, const float* lng_beta, int gaze_dim,
+                        const float* mask, const uint8_t* drop_mask, float drop_scale, const float* ln1_gamma,
+                        const float* ln1_beta, float* rgb_out, float* dep_pre_out, float* mean_d, float* rstd_d,
+                        float* dep_out, float* gz_pre_out, float* mean_g, float* rstd_g, float* gz_out, float* x0, float* h1,
+                        float* m1, float* r1, int N, int H, void* stream);
+int r3d_embed_fuse3_bwd(const float* d_h1, const float* x0, const float* m1, const float* r1, const float* ln1_gamma,
+                        const float* add1, const float* add2, const uint8_t* drop_mask, float drop_scale, const float* mask,
+                        const float* rgb, const float* dep_pre, const float* mean_d, const float* rstd_d,
+                        const float* lnd_gamma, const float* lnd_beta, const float* gz_pre, const float* mean_g,
+                        const float* rstd_g, const float* lng_gamma, const float* lng_beta, float* d_rgb_pre,
+                        float* d_dep_pre, float* d_gz_pre, float* ws_n1, float* ws_dep, float* ws_gz, int N, int H,
+                        void* stream);
 
 /* ---- the BN-blend token fuser of model/futr_safuser_batchnormalization.py:38-76 -------------------------
  * r3d_bn_stats     : BatchNorm1d statistics of both embeddings [N, C] (batch statistics + running-stat update when

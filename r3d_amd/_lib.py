@@ -249,6 +249,8 @@ _SIGNATURES = {
                                    _I, _P, _I, _I, _P], C.c_int),
     "r3d_embed_fuse_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
                            C.c_int),
+    "r3d_embed_fuse3_fwd": ([_P, _I, _P, _P, _I] + [_P] * 8 + [_I, _P, _P, _F] + [_P] * 15 + [_I, _I, _P], C.c_int),
+    "r3d_embed_fuse3_bwd": ([_P] * 8 + [_F] + [_P] * 18 + [_I, _I, _P], C.c_int),
     "r3d_bn_stats": ([_P] * 13 + [_I, _I, _I, _F, _P], C.c_int),
     "r3d_bn_blend_fwd": ([_P] * 12 + [_F] + [_P] * 6 + [_I, _I, _P], C.c_int),
     "r3d_bn_blend_bwd": ([_P] * 7 + [_F] + [_P] * 17 + [_I, _I, _P], C.c_int),

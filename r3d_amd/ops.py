@@ -1338,6 +1338,67 @@ def triple_mean_bwd(d_out, dy):
     check(_lib.load().r3d_triple_mean_bwd(_p(d_out), _p(dy), N, Cc, _stream()), "r3d_triple_mean_bwd")
 
 
+# ---- the three-modality embedding seam (csrc/fuse3_seam.hip) -----------------------------------------------------------
+FUSE3_MAX_GAZE = 8              # csrc/fuse3_seam.hip: kFuse3MaxGaze
+
+
+def _fuse3_check(who, N, H, rows_n, rows_3n, per_n, per_3n, vecs, mask, drop, gaze=None, G=None):
+    """Operands of the three-modality seam: every tensor float32, on the device, contiguous and of the exact size the
+    kernel indexes (it holds a channel row in one wave's registers: H <= 1024).  gaze [N, G]: the forward's operand only."""
+    if not 0 < H <= 1024:
+        raise ValueError(f"hidden {H}: the {who}'s seam holds a channel row in one wave's registers (<= 1024)")
+    if gaze is not None and not 1 <= G <= FUSE3_MAX_GAZE:
+        raise ValueError(f"gaze_dim {G}: the {who}'s seam takes 1 to {FUSE3_MAX_GAZE} gaze inputs per frame")
+    assert N > 0 and 3 * N * H < 2 ** 31, f"{who}: 3 * N * hidden < 2^31"
+    for group, k in ((rows_n, N * H), (rows_3n, 3 * N * H), (per_n, N), (per_3n, 3 * N), (vecs, H), ((mask,), 3 * H),
+                     (((gaze,), N * G) if gaze is not None else ((), 0))):
+        for t in group:
+            assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == k, \
+                f"{who}: expected a contiguous float32 device tensor of {k} elements, got {tuple(t.shape)} {t.dtype}"
+    assert drop is None or (drop.dtype == torch.uint8 and drop.is_cuda and drop.is_contiguous() and drop.numel() >= 3 * N * H), \
+        f"{who}: drop_mask must be a contiguous uint8 device tensor over x0's {3 * N * H} elements"
+
+
+def embed_fuse3_fwd(rgb_src, ns_r, bias_r, dep_src, ns_d, bias_d, lnd_g, lnd_b, gaze, w_g, b_g, lng_g, lng_b, mask, drop,
+                    drop_scale, ln1_g, ln1_b, rgb_out, dep_pre_out, mean_d, rstd_d, dep_out, gz_pre_out, mean_g, rstd_g,
+                    gz_out, x0, h1, m1, r1):
+    """Three-modality embedding seam, forward (csrc/fuse3_seam.hip): slab sums of both projections + bias / ReLU / depth
+    LayerNorm + ReLU (the conventions of embed_fuse_fwd), gz = relu(LN_g(b_g + w_g . gaze)), cyclic exchange with mask
+    [3, H] + embd_drop, norm1 -> x0, h1 [3N, H] (rows 3n + m), m1 / r1 [3N]."""
+    N, H = dep_out.shape
+    G = w_g.shape[1]
+    assert tuple(w_g.shape) == (H, G) and w_g.dtype == torch.float32 and w_g.is_cuda and w_g.is_contiguous()
+    vecs = [lnd_g, lnd_b, b_g, lng_g, lng_b, ln1_g, ln1_b] + ([bias_r] if bias_r is not None else []) + (
+        [bias_d] if bias_d is not None else [])
+    _fuse3_check("embed_fuse3_fwd", N, H, (rgb_out, dep_pre_out, dep_out, gz_pre_out, gz_out), (x0, h1),
+                 (mean_d, rstd_d, mean_g, rstd_g), (m1, r1), vecs, mask, drop, gaze=gaze, G=G)
+    assert ns_r >= 0 and ns_d >= 1 and (ns_r == 0 or bias_r is not None)
+    for t, k in ((rgb_src, max(ns_r, 1) * N * H), (dep_src, ns_d * N * H)):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() >= k
+    check(_lib.load().r3d_embed_fuse3_fwd(_p(rgb_src), ns_r, _p(bias_r), _p(dep_src), ns_d, _p(bias_d), _p(lnd_g), _p(lnd_b),
+                                          _p(gaze), _p(w_g), _p(b_g), _p(lng_g), _p(lng_b), G, _p(mask), _p(drop), drop_scale,
+                                          _p(ln1_g), _p(ln1_b), _p(rgb_out), _p(dep_pre_out), _p(mean_d), _p(rstd_d),
+                                          _p(dep_out), _p(gz_pre_out), _p(mean_g), _p(rstd_g), _p(gz_out), _p(x0), _p(h1),
+                                          _p(m1), _p(r1), N, H, _stream()), "r3d_embed_fuse3_fwd")
+
+
+def embed_fuse3_bwd(d_h1, x0, m1, r1, ln1_g, add1, add2, drop, drop_scale, mask, rgb, dep_pre, mean_d, rstd_d, lnd_g, lnd_b,
+                    gz_pre, mean_g, rstd_g, lng_g, lng_b, d_rgb_pre, d_dep_pre, d_gz_pre, ws_n1, ws_dep, ws_gz):
+    """Adjoint of embed_fuse3_fwd: d_rgb_pre, d_dep_pre, d_gz_pre [N, H] and the per-frame (dgamma, dbeta) partials
+    ws_n1 / ws_dep / ws_gz [N][2][H] (LnFinalizeGroup job with rows = -N).  add1 / add2: optional residual gradients."""
+    N, H = rgb.shape
+    big = [d_h1, x0] + [t for t in (add1, add2) if t is not None]
+    _fuse3_check("embed_fuse3_bwd", N, H, (rgb, dep_pre, gz_pre, d_rgb_pre, d_dep_pre, d_gz_pre), big,
+                 (mean_d, rstd_d, mean_g, rstd_g), (m1, r1), (ln1_g, lnd_g, lnd_b, lng_g, lng_b), mask, drop)
+    for t in (ws_n1, ws_dep, ws_gz):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() >= 2 * N * H
+    check(_lib.load().r3d_embed_fuse3_bwd(_p(d_h1), _p(x0), _p(m1), _p(r1), _p(ln1_g), _p(add1), _p(add2), _p(drop), drop_scale,
+                                          _p(mask), _p(rgb), _p(dep_pre), _p(mean_d), _p(rstd_d), _p(lnd_g), _p(lnd_b),
+                                          _p(gz_pre), _p(mean_g), _p(rstd_g), _p(lng_g), _p(lng_b), _p(d_rgb_pre),
+                                          _p(d_dep_pre), _p(d_gz_pre), _p(ws_n1), _p(ws_dep), _p(ws_gz), N, H, _stream()),
+          "r3d_embed_fuse3_bwd")
+
+
 # ----------------------------------------------------------------------------------------------------------
 # bidirectional LSTM layer (model/rnn.py)
 # ----------------------------------------------------------------------------------------------------------

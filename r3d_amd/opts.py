@@ -84,6 +84,9 @@ parser.add_argument("--supcon_weight", type=float, default=0.0,
                          "and padded frames skipped because unnormalised rnn_fc outputs are exactly the input on which the "
                          "reference's SupConLoss returns nan, so the parity of this term is pinned only against the float64 "
                          "restatement (tests/supcon_oracle.py).  The other loops refuse a non-zero value")
+parser.add_argument("--gaze_dim", type=int, default=2,
+                    help="three-modality model (model/futr_safuser_tokenfusion3.py) only: values per frame of the gaze track "
+                         "(1 to 8; the gaze data set yields [S, 2] tracks)")
 
 
 def refuse_supcon_weight(args, loop):

@@ -258,6 +258,9 @@ class DataParallelStep:
         """sync_bn (BN-blend variant only): batch statistics over the GLOBAL batch, as the single-process reference sees it
         (False = per-rank statistics, what nn.DataParallel gives the reference)."""
         refuse_tall_route(engine, "a data-parallel step")
+        refuse = getattr(engine, "refuse_data_parallel", None)      # (an engine that runs on one GPU only says so here)
+        if refuse is not None:
+            refuse()
         self.eng = engine
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1

@@ -30,10 +30,23 @@ NTU_EXCLUDE_CLASS_IDX = 120                   # evaluation/predict_nturgbd.py:33
 NTU_DATASET_DIRS = dict(DATASET_DIRS, nturgbd="nturgbd")                                # predict_nturgbd.py:231-232
 
 
+def refuse_gaze_model(model, who):
+    """The three-modality model (model/futr_safuser_tokenfusion3.py) needs a gaze track per frame, and the per-video
+    dataset layout read here has no gaze file: a ValueError before anything runs."""
+    m = model
+    while hasattr(m, "module") and not hasattr(m, "gaze_projection"):
+        m = m.module
+    if hasattr(m, "gaze_projection"):
+        raise ValueError(f"{who}: the three-modality (RGB + depth + gaze) model is not served: the per-video dataset layout "
+                         f"(groundTruth / features_img / features_depth) has no gaze file to read; call model(inputs, "
+                         f"depth_features, gaze, mode='test') with a gaze track of your own")
+
+
 @torch.no_grad()
 def predict_clip(model, features, depth_features, future_len, none_idx=None):
     """features [T, D] float32, depth_features [T, ...] (frames of one clip, already sub-sampled), on the model's device.
     Returns dict(seg_labels [T], action_labels [Q], frames [future_len], outputs=<the model's output dict>)."""
+    refuse_gaze_model(model, "predict_clip()")
     was_training = model.training
     model.eval()
     try:
@@ -124,6 +137,7 @@ def predict_nturgbd(model, vid_list, args, obs_p, n_class, actions_dict, device,
 
 def _predict(model, vid_list, args, obs_p, n_class, actions_dict, device, data_path, log_dir, reader, details, exclude_idx,
              dataset_dirs, features_dir, with_depth):
+    refuse_gaze_model(model, "predict()")
     acc = seg_acc = 0.0
     idx = 0
     model.eval()

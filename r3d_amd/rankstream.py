@@ -20,6 +20,16 @@ import torch
 from . import ops
 
 BUFFERS = {"rgb": "rgb", "depth": "dep", "fused": "fused"}      # public name -> attribute of the engine's workspace
+BUFFERS3 = {"rgb": "rgb", "depth": "dep", "gaze": "gaze", "fused": "fused"}     # the three-modality model's
+
+
+def _is_m3(core):
+    return hasattr(core, "gaze_projection")
+
+
+def buffers_of(model):
+    """public name -> workspace attribute for this model: BUFFERS, or BUFFERS3 for the three-modality model"""
+    return BUFFERS3 if _is_m3(_fuser_core(model)) else BUFFERS
 
 
 class StreamingRank:
@@ -95,15 +105,19 @@ def _fuser_core(model):
     return m
 
 
-def attach(model, which=("rgb", "depth", "fused"), lanes=8):
+def attach(model, which=None, lanes=8):
     """Accumulators (name -> StreamingRank) fed by every forward of the model's engine until detach().  Raises ValueError
-    for a model without a fused token matrix, before anything is allocated."""
+    for a model without a fused token matrix, before anything is allocated.  which: default rgb, depth, fused (and gaze
+    for the three-modality model)."""
+    bufs = buffers_of(model)
+    if which is None:
+        which = tuple(bufs)
     for name in which:
-        if name not in BUFFERS:
-            raise ValueError(f"measure_rank: unknown representation {name!r} (one of {sorted(BUFFERS)})")
+        if name not in bufs:
+            raise ValueError(f"measure_rank: unknown representation {name!r} (one of {sorted(bufs)})")
     eng = _fuser_core(model).engine()
     accs = {name: StreamingRank(eng.H, eng.device, lanes) for name in which}
-    eng.rank_stream = [(BUFFERS[name], acc) for name, acc in accs.items()]
+    eng.rank_stream = [(bufs[name], acc) for name, acc in accs.items()]
     return accs
 
 
@@ -111,7 +125,7 @@ def detach(model):
     _fuser_core(model).engine().rank_stream = None
 
 
-def measure_rank(model, loader, device, which=("rgb", "depth", "fused")):
+def measure_rank(model, loader, device, which=None):
     """Effective rank of the RGB embedding, the depth embedding and the fused tokens over every frame of `loader`
     (anything validate() accepts), padded frames (past_label == pad_idx) left out: {name: dict(erank, sigma, rows)}.
     The validation forward of each batch feeds the accumulators; one device->host read per name at the end.
@@ -126,14 +140,19 @@ def measure_rank(model, loader, device, which=("rgb", "depth", "fused")):
             for data in loader:
                 if data is None:
                     continue
-                features, depth_features, past_label, _, _ = _to_dev(data, eng.device)
-                eng.forward(features, depth_features, past_label, "val", training=False, need_grad=False)
+                batch = _to_dev(data, eng.device, gaze=_is_m3(core))
+                kw = dict(gaze=batch[5]) if len(batch) == 6 else {}
+                eng.forward(batch[0], batch[1], batch[2], "val", training=False, need_grad=False, **kw)
     finally:
         detach(core)
     return {name: acc.finalize() for name, acc in accs.items()}
 
 
 def report_line(results):
-    """The line train() prints after validate() with --erank_report."""
+    """The line train() prints after validate() with --erank_report (the three-modality model: four names)."""
+    if "gaze" in results:
+        return "Effective rank over %d frames: rgb %.3f, depth %.3f, gaze %.3f, fused %.3f" % (
+            results["fused"]["rows"], results["rgb"]["erank"], results["depth"]["erank"], results["gaze"]["erank"],
+            results["fused"]["erank"])
     return "Effective rank over %d frames: rgb %.3f, depth %.3f, fused %.3f" % (
         results["fused"]["rows"], results["rgb"]["erank"], results["depth"]["erank"], results["fused"]["erank"])

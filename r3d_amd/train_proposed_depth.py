@@ -50,11 +50,27 @@ def weighted_accuracy(pred, gold, pad_idx, t_n_labels, weight_same=1.0, weight_d
     return float((pred.eq(gold) & mask).sum()) / total if total > 0 else 0
 
 
-def _to_dev(data, device):
-    features, depth_features, past_label, trans_dur_future, trans_future_target = data
-    return (features.to(device=device, dtype=torch.float32), depth_features.to(device=device, dtype=torch.float32),
-            past_label.to(device).long().contiguous(), trans_dur_future.to(device=device, dtype=torch.float32).contiguous(),
-            trans_future_target.to(device).long().contiguous())
+def _is_m3(core):
+    """the three-modality model (model/futr_safuser_tokenfusion3.py): its batches carry a gaze track as a sixth element"""
+    return hasattr(core, "gaze_projection")
+
+
+def _to_dev(data, device, gaze=False):
+    """gaze: the model is the three-modality one.  Its batches are 6-tuples (gaze [B, S, gaze_dim] appended to today's five);
+    every other model's are 5-tuples.  The wrong arity for the model is a ValueError."""
+    if len(data) != (6 if gaze else 5):
+        if gaze:
+            raise ValueError(f"the three-modality model takes 6-element batches (features, depth_features, past_label, "
+                             f"trans_dur_future, trans_future_target, gaze); got {len(data)} elements")
+        raise ValueError(f"a batch of {len(data)} elements: only the three-modality model "
+                         f"(model/futr_safuser_tokenfusion3.py) takes a gaze track; this model takes 5-element batches")
+    features, depth_features, past_label, trans_dur_future, trans_future_target = data[:5]
+    out = (features.to(device=device, dtype=torch.float32), depth_features.to(device=device, dtype=torch.float32),
+           past_label.to(device).long().contiguous(), trans_dur_future.to(device=device, dtype=torch.float32).contiguous(),
+           trans_future_target.to(device).long().contiguous())
+    if gaze:
+        out += (data[5].to(device=device, dtype=torch.float32).contiguous(),)
+    return out
 
 
 def _graph_key(eng, hyper):
@@ -166,7 +182,8 @@ class _GraphedSteps:
 
     def _enqueue(self, buf, lr, hyper, training):
         eng = self.eng
-        feats, depth, lab, dur, tgt = buf
+        feats, depth, lab, dur, tgt = buf[:5]
+        kw = dict(gaze=buf[5]) if len(buf) == 6 else {}          # (the three-modality model: one more static buffer)
         wd, betas, eps = hyper
         # forward -> losses -> backward back to back: the decoder tail, the losses and the tail's backward are one launch
         # (defer_tail), and the loss statistics -- with their epoch sums -- are reduced by one workgroup of the AdamW launch
@@ -175,7 +192,7 @@ class _GraphedSteps:
             keep = (eng.defer_tail, eng.defer_loss_reduce, eng.loss_acc)
             eng.defer_tail, eng.defer_loss_reduce, eng.loss_acc = True, True, (self.acc_loss, self.acc_cnt)
         try:
-            eng.forward(feats, depth, lab, "train", training=training)
+            eng.forward(feats, depth, lab, "train", training=training, **kw)
             loss, counts = eng.losses(lab, tgt, dur, tick=True)
             folded = getattr(eng, "_loss_pending", None) is not None
         finally:
@@ -332,8 +349,10 @@ def validate(model, val_loader, criterion, pad_idx, device):
         for data in val_loader:
             if data is None:
                 continue
-            features, depth_features, past_label, trans_dur_future, trans_future_target = _to_dev(data, eng.device)
-            out = eng.forward(features, depth_features, past_label, "val", training=False, need_grad=False)
+            batch = _to_dev(data, eng.device, gaze=_is_m3(core))
+            features, depth_features, past_label, trans_dur_future, trans_future_target = batch[:5]
+            kw = dict(gaze=batch[5]) if len(batch) == 6 else {}
+            out = eng.forward(features, depth_features, past_label, "val", training=False, need_grad=False, **kw)
             loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, with_grad=False, val_mode=True)
             lv, cv = loss.cpu(), counts.cpu()                       # one readback per validation clip
             val_loss += float(lv[1] + lv[2])                        # action CE + duration (:86,100)
@@ -363,6 +382,12 @@ def _print_erank(eng):
 def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
     refuse_supcon_weight(args, "train_proposed_depth")
     core = _unwrap(model)
+    m3 = _is_m3(core)
+    if m3:          # (before anything is moved or allocated: what the three-modality engine does not run)
+        from .engine_m3 import check_m3_args
+        check_m3_args(pixel_shard=bool(getattr(args, "pixel_shard", False)),
+                      parallel=bool(dist.is_available() and dist.is_initialized() and
+                                    (dist.get_world_size() > 1 or os.environ.get("R3D_REHEARSE_DIST") == "1")))
     model.to(device)
     model.train()
     eng = core.engine()
@@ -457,13 +482,15 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         for i, data in (enumerate(train_loader) if sharded is None else ()):
             if data is None:
                 continue
-            features, depth_features, past_label, trans_dur_future, trans_future_target = _to_dev(data, eng.device)
+            batch = _to_dev(data, eng.device, gaze=m3)
+            features, depth_features, past_label, trans_dur_future, trans_future_target = batch[:5]
+            kw = dict(gaze=batch[5]) if m3 else {}
             if len(features) < min_batch:
                 continue
             g = optimizer.param_groups[0]
             if graphed is not None and isinstance(optimizer, FlatAdamW):
                 graphed.step([features.contiguous(), depth_features.contiguous(), past_label.contiguous(),
-                              trans_dur_future.contiguous(), trans_future_target.contiguous()], g["lr"],
+                              trans_dur_future.contiguous(), trans_future_target.contiguous()] + list(batch[5:]), g["lr"],
                              (g["weight_decay"], tuple(g["betas"]), g["eps"]), model.training)
                 n_steps += 1
                 if erank_every and n_steps % erank_every == 0:
@@ -471,7 +498,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
                 continue
             if dp is not None:
                 dp.prepare_duration_denominator(trans_dur_future, pad_idx)
-            eng.forward(features, depth_features, past_label, "train", training=model.training)
+            eng.forward(features, depth_features, past_label, "train", training=model.training, **kw)
             fused_opt = isinstance(optimizer, FlatAdamW)
             loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, tick=fused_opt)
             fuse = bool(fused_opt and dp is None and hasattr(eng, "depth_adamw_fusable") and eng.depth_adamw_fusable())
@@ -510,7 +537,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         if rank_accs is not None:
             for acc in rank_accs.values():
                 acc.reset()
-            eng.rank_stream = [(rankstream.BUFFERS[name], acc) for name, acc in rank_accs.items()]
+            eng.rank_stream = [(rankstream.buffers_of(core)[name], acc) for name, acc in rank_accs.items()]
         try:
             val_loss, val_acc, weight_acc = validate(model, val_loader, criterion, pad_idx, device)
         finally:
