@@ -20,6 +20,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // edge -- s_waitcnt vmcnt(0) on the newest loads every iteration (found in gemm_bf3_nt_kernel's ISA, round 3)
 typedef float f32x4n __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
 
 // Two consecutive-k values -> the three bf16 terms of each, already packed (element k in the low half of the dword:
 // little-endian vector order).  Truncation split: h = the top 16 bits of x (v_perm_b32 takes the high halves of the pair
@@ -74,6 +75,33 @@ __device__ __forceinline__ f32x16 mfma_bf3(const uint4 ah, const uint4 am, const
     return acc;
 }
 
+// Profiling builds only (tools/nt_stub_probe.sh; results wrong by construction): R3D_NT_PROBE bits -- 1 consumers do nothing but
+// the barriers, 8 consumers read their operands but issue no MFMA, 2 producers store the raw bits (no split), 4 producers
+// store nothing (the loads are still waited for); 16 timeline: threads 0 (consumer wave 0) and 256 (producer wave 4) of workgroup 16
+// store wall_clock64() (100 MHz) marks behind the slabs (the caller's workspace must have room: tools/nt_timeline.py).
+#ifndef R3D_NT_PROBE
+#define R3D_NT_PROBE 0
+#endif
+#if R3D_NT_PROBE & 16
+#define R3D_NT_MARK(K) do { if (blockIdx.x == 16 && (threadIdx.x & 255) == 0)                                                       \
+        reinterpret_cast<unsigned long long*>(d.partial + (size_t)NG * d.M * d.N)[(threadIdx.x >> 8) * 64 + (K)] = wall_clock64(); } while (0)
+#define R3D_NT_CYC(K) do { if (blockIdx.x == 16 && (threadIdx.x & 255) == 0)                                                        \
+        reinterpret_cast<unsigned long long*>(d.partial + (size_t)NG * d.M * d.N)[(threadIdx.x >> 8) * 64 + (K)] = __builtin_readcyclecounter(); } while (0)
+// (the weight-gradient kernel has no workspace: its marks go behind the C matrix, whose allocation the probe tool oversizes)
+#define R3D_TN_MARK(K) do { if (blockIdx.x == 16 && (threadIdx.x & 255) == 0)                                                       \
+        reinterpret_cast<unsigned long long*>(d.C + (size_t)d.M * d.ldc)[(threadIdx.x >> 8) * 64 + (K)] = wall_clock64(); } while (0)
+#else
+#define R3D_NT_MARK(K) do { } while (0)
+#define R3D_NT_CYC(K) do { } while (0)
+#define R3D_TN_MARK(K) do { } while (0)
+#endif
+// (marks of the panel kernel below, read by tools/wgrad_panel_timeline.py: nothing may be scheduled across one, and only the
+//  64 slots of a role exist)
+#if R3D_NT_PROBE & 16
+#define R3D_WG_MARK(K) do { __builtin_amdgcn_sched_barrier(0); if ((K) < 64) R3D_TN_MARK(K); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define R3D_WG_MARK(K) do { } while (0)
+#endif
 // ---------------------------------------------------------------------------------------------------------
 // Weight gradient of a WIDE layer from FEW rows, C[M, N] = A^T . B with A [K, M], B [K, N], K <= 128, M <= 128, N huge
 // (same contract as wgrad_panel_kernel in gemm_f32.hip: persistent workgroups over 64-column panels of B).
@@ -83,11 +111,13 @@ __device__ __forceinline__ f32x16 mfma_bf3(const uint4 ah, const uint4 am, const
 // the workgroup is split by ROLE:
 //   waves 0-3  consumers: wave w owns output rows 32 w .. 32 w + 31 for both 32-column halves of the panel.  A^T for
 //              its rows (all K, three bf16 planes) stays in 96 registers; per panel 8 k-steps x 2 halves x 6 products
-//              = 96 MFMAs; the C stores of the previous panel are issued in between (4 per k-step) so that they
-//              trickle into the memory pipe under the matrix cores instead of stalling the wave in one burst;
+//              = 96 MFMAs; the finished tile goes to an LDS image (ctile) between the turn's two barriers;
 //   waves 4-7  producers: 256 threads fetch the next panels (three register stages: the loads of panel p + 3 are in
 //              flight while p is multiplied), split them and write the [n][k] bf16 images -- their VALU / LDS work
-//              shares each SIMD with one consumer wave whose time goes to the matrix core.
+//              shares each SIMD with one consumer wave whose time goes to the matrix core -- and drain the previous
+//              panel's C tile with 16-byte row-contiguous WRITE-THROUGH stores (see drain_c).
+// Storing C straight from the accumulators between the next panel's MFMAs (no C tile, one barrier per turn) was built
+// three ways and measured no faster in the step: profiles/wgrad_panel_timeline.txt.
 // The operands are M / N-contiguous in memory but the bf16 MFMA wants 8 consecutive k per lane, so the split happens on
 // the way into LDS: a producer thread loads 4 (k) x 4 (n) blocks, splits them and writes, per column and plane, four
 // k-consecutive bf16 as one 8-byte store into a [n][k] image of row stride 136 bf16 (= 68 dwords: 16-byte operand reads
@@ -144,6 +174,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_panel_bf3_kernel(const r3d_gemm_
         const int wrow = wave * 32 + 4 * lhi;
         const int x0 = (l31 >> 4) & 3, x1 = ((32 + l31) >> 4) & 3;  // octet swizzle of rows l31 and 32 + l31
         for (int p = 0; p < nturn; ++p) {
+            R3D_WG_MARK(1 + 5 * p);
             const unsigned short* cur = (p & 1) ? img1 : img0;
             f32x16 acc0, acc1;
 #pragma unroll
@@ -176,7 +207,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_panel_bf3_kernel(const r3d_gemm_
 #undef R3D_MM
 #undef R3D_BF
             }
+            R3D_WG_MARK(2 + 5 * p);
             __syncthreads();                                        // mid-turn: the producers have drained the C tile
+            R3D_WG_MARK(3 + 5 * p);
             // the panel's C tile goes to LDS; the producers stream it out with 16-byte row-contiguous stores next turn
             // C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
@@ -185,7 +218,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_panel_bf3_kernel(const r3d_gemm_
                 ctile[m * kP3CS + l31] = acc0[r];
                 ctile[m * kP3CS + 32 + l31] = acc1[r];
             }
+            R3D_WG_MARK(4 + 5 * p);
             __syncthreads();
+            R3D_WG_MARK(5 + 5 * p);
         }
         __syncthreads();                                            // (the producers' extra half turn: last C tile out)
     } else {
@@ -231,29 +266,50 @@ __global__ __launch_bounds__(512, 1) void wgrad_panel_bf3_kernel(const r3d_gemm_
         // (every load is unconditional, turn indices clamped: a load under a branch makes hipcc wait vmcnt(0) at the next
         //  use, which exposes the round trip of the loads issued one turn earlier)
         const int lastt = nturn - 1;
+        R3D_WG_MARK(0);
         load_panel(st0, 0);                                         // the first loads go out before anything else
         load_panel(st1, min(1, lastt));
         load_panel(st2, min(2, lastt));
         store_panel(img0, st0, 0);
         __syncthreads();                                            // B3
-        // C tile of the previous turn: LDS -> memory, 128 rows x 256 bytes, 8 float4 per thread
+        // C tile of the previous turn: LDS -> memory, 128 rows x 256 bytes, 8 float4 per thread.
+        // The stores are WRITE-THROUGH (buffer_store_dwordx4 sc1: aux 16 of the raw buffer store).  Plain stores leave the whole
+        // gradient (25.7 MB at the headline shape) dirty in the XCDs' L2s, which hold all of it, and the write-back is then paid
+        // in one piece where the kernel ends: 18.4 us per launch against 15.5 us with these stores, same box, alternating
+        // runs (profiles/wgrad_panel_speed.json); written through, the tiles leave while the next panels are multiplied.
+        // (a buffer offset has 32 bits: a C whose last row starts beyond 2 GB -- ldc >= 2^22 -- keeps the plain stores)
+        const bool c_wt = (size_t)d.ldc < ((size_t)1 << 22);
+        const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(d.C, 0, 0x7fffffff, 0x00020000);
         auto drain_c = [&](int turn_done) {
             const int n0 = pid(turn_done) * kP3N;
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const int f = pt + 256 * t, m = f >> 4, q = (f & 15) << 2;
                 const float4 v = *reinterpret_cast<const float4*>(ctile + m * kP3CS + q);
-                if (m < M && n0 + q < N) *reinterpret_cast<float4*>(d.C + (size_t)m * d.ldc + n0 + q) = v;
+                if (m < M && n0 + q < N) {
+                    const size_t e = (size_t)m * d.ldc + n0 + q;
+                    if (c_wt) {
+                        const f32x4n vv = {v.x, v.y, v.z, v.w};
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4n, vv), crsrc, (int)(e * sizeof(float)), 0, 16);
+                    } else {
+                        *reinterpret_cast<float4*>(d.C + e) = v;
+                    }
+                }
             }
         };
         // turn p: the C tile of panel p - 1 leaves, panel p + 1 (a register stage) goes to the other image, the stage
         // panel p came from is refilled with panel p + 3.  Stage of panel q = q % 3; 6 = lcm(2 images, 3 stages).
         auto turn = [&](int p, unsigned short* oth, f32x4n* nxt, f32x4n* mine) {
+            R3D_WG_MARK(1 + 5 * p);
             if (p > 0) drain_c(p - 1);
+            R3D_WG_MARK(2 + 5 * p);
             if (p + 1 < nturn) store_panel(oth, nxt, p + 1);
             load_panel(mine, min(p + 3, lastt));
+            R3D_WG_MARK(3 + 5 * p);
             __syncthreads();                                        // mid-turn
+            R3D_WG_MARK(4 + 5 * p);
             __syncthreads();
+            R3D_WG_MARK(5 + 5 * p);
         };
         for (int p = 0; p < nturn; p += 6) {
             turn(p, img1, st1, st0);
@@ -264,6 +320,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_panel_bf3_kernel(const r3d_gemm_
             if (p + 5 < nturn) turn(p + 5, img0, st0, st2);
         }
         drain_c(nturn - 1);
+        R3D_WG_MARK(30);
         __syncthreads();
     }
 }
@@ -280,26 +337,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_panel_bf3_kernel(const r3d_gemm_
 // Output: raw fp32 slabs exactly as gemm_f32_kernel leaves them for split-K (the caller's reducer applies bias / LayerNorm /
 // the epilogue), placed XCD-aware (the tiles of one K-split share linear id mod 8).
 // ---------------------------------------------------------------------------------------------------------
-// Profiling builds only (tools/nt_stub_probe.sh; results wrong by construction): R3D_NT_PROBE bits -- 1 consumers do nothing but
-// the barriers, 8 consumers read their operands but issue no MFMA, 2 producers store the raw bits (no split), 4 producers
-// store nothing (the loads are still waited for); 16 timeline: threads 0 (consumer wave 0) and 256 (producer wave 4) of workgroup 16
-// store wall_clock64() (100 MHz) marks behind the slabs (the caller's workspace must have room: tools/nt_timeline.py).
-#ifndef R3D_NT_PROBE
-#define R3D_NT_PROBE 0
-#endif
-#if R3D_NT_PROBE & 16
-#define R3D_NT_MARK(K) do { if (blockIdx.x == 16 && (threadIdx.x & 255) == 0)                                                       \
-        reinterpret_cast<unsigned long long*>(d.partial + (size_t)NG * d.M * d.N)[(threadIdx.x >> 8) * 64 + (K)] = wall_clock64(); } while (0)
-#define R3D_NT_CYC(K) do { if (blockIdx.x == 16 && (threadIdx.x & 255) == 0)                                                        \
-        reinterpret_cast<unsigned long long*>(d.partial + (size_t)NG * d.M * d.N)[(threadIdx.x >> 8) * 64 + (K)] = __builtin_readcyclecounter(); } while (0)
-// (the weight-gradient kernel has no workspace: its marks go behind the C matrix, whose allocation the probe tool oversizes)
-#define R3D_TN_MARK(K) do { if (blockIdx.x == 16 && (threadIdx.x & 255) == 0)                                                       \
-        reinterpret_cast<unsigned long long*>(d.C + (size_t)d.M * d.ldc)[(threadIdx.x >> 8) * 64 + (K)] = wall_clock64(); } while (0)
-#else
-#define R3D_NT_MARK(K) do { } while (0)
-#define R3D_NT_CYC(K) do { } while (0)
-#define R3D_TN_MARK(K) do { } while (0)
-#endif
 // One MFMA, then three VALU instructions, 24 times; the six LDS stores and four loads of the step spread between
 // (sched_group_barrier masks: 0x008 MFMA, 0x002 VALU, 0x200 DS write, 0x020 VMEM read).  R3D_NTU_NOSCHED: leave it to hipcc.
 #ifdef R3D_NTU_NOSCHED

@@ -7,4 +7,5 @@ python tools/nt_timeline.py 8 61 2>/dev/null
 python tools/nt_timeline.py 9 196 2>/dev/null
 python tools/nt_timeline.py 11 196 2>/dev/null
 python tools/tn_timeline.py 2>/dev/null
+python tools/wgrad_panel_timeline.py 2>/dev/null
 python -m r3d_amd.build --force > /dev/null 2>&1
