@@ -756,7 +756,7 @@ template <int LA, int LB, int BM, int BN, int BK, int WM, int WN, int WK>
 static int launch_cfg(const r3d_gemm_desc& d, int nsplit, hipStream_t s) {
     const int tm = r3d_cdiv(d.M, BM), tn = r3d_cdiv(d.N, BN);
     dim3 grid(tm * tn, nsplit, 1);
-    int mode = 0, G = 1, NG = 1;
+    int mode = 0, G = 1, NG = 1;      // (this rule is mirrored by grid_mode() in tests/gemm_f32_cases.py: change both together)
     if (nsplit > 1 && tm * tn > 1 && tm * tn <= 32) { mode = 1; G = tm * tn; NG = nsplit; }
     else if (nsplit == 1 && tm >= 2 && tm <= 16 && tn >= 16) { mode = 2; G = tm; NG = tn; }
     else if (nsplit == 1 && tn >= 2 && tn <= 16 && tm >= 16) { mode = 3; G = tn; NG = tm; }
