@@ -1,0 +1,272 @@
+"""The post-norm transformer decoder (reference transformer.py:281-330) composed launch by launch from ops.gemm, ops.mha_* and
+ops.layernorm_*, and the engine plumbing around it, shared by the query engines engine_unsup, engine_l3 and engine_m3 (the
+token-fusion engine's decoder is interleaved with streams, chain kernels and deferred tails: engine.py keeps its own).
+
+One decoder serves the three: `rows` query rows (B clips x Tq queries) attend to themselves and to the B x S rows of `mem`
+(+ pos_embedding[:S]).  What differs comes in as arguments:
+  qpos, qmod   the query position and its broadcast modulus -- an activation [rows, H] with modulus rows, or the query_embed
+               parameter [Q, H] with modulus Q;
+  g_qpos       where the query position's gradient goes -- None: added into w.d_qpos through w.d_qtmp (an activation: it flows
+               on into the engine's branch); a parameter's gradient tensor: folded over the clips with rowmod_sum;
+  mem          the memory (w.mem or w.fused);
+  w.route      "core" (r3d_mha_core_*, the probabilities kept) or "tiled" (r3d_mha_tiled_*, lse kept, probabilities recomputed).
+Kernels are called as attributes of the ops module: the tests patch them there and count the calls."""
+import torch
+
+from . import ops
+from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
+from .engine import DROP_P
+
+DROP_SCALE = 1.0 / (1.0 - DROP_P)
+
+
+# ---- buffers ------------------------------------------------------------------------------------------------------------
+def decoder_drop_sizes(L, B, heads, H, rows, Tq, Tk):
+    """{site: numel} of the decoder's dropout keep-masks, layer by layer."""
+    sizes = {}
+    for l in range(L):
+        sizes.update({f"sa_p{l}": B * heads * Tq * Tq, f"ca_p{l}": B * heads * Tq * Tk, f"d1_{l}": rows * H,
+                      f"d2_{l}": rows * H, f"d3_{l}": rows * H, f"ff_{l}": rows * 4 * H})
+    return sizes
+
+
+def drop_pool(sizes, device):
+    """(pool, {site: view}): one uint8 pool that a single Philox launch fills, every site at a 16-byte aligned offset in the
+    order of `sizes` -- the order is behaviour: the mask a site receives depends on its offset."""
+    tot = sum((v + 15) // 16 * 16 for v in sizes.values())
+    pool = torch.ones(tot, dtype=torch.uint8, device=device)
+    views, o = {}, 0
+    for k, v in sizes.items():
+        views[k] = pool[o:o + v]
+        o += (v + 15) // 16 * 16
+    return pool, views
+
+
+def decoder_buffers(w, eng, Tq, route, train, own_drop_sizes):
+    """The decoder's activations (w.tgt0, w.layers, w.tgtF ...), with `train` its gradients (w.glayers, w.d_mp ...) and the
+    dropout pool (the engine's own sites first, then the layers), on the shape workspace w (w.B, w.S, w.N are set)."""
+    dev, H, L, heads, B, S, N = eng.device, eng.H, eng.L, eng.heads, w.B, w.S, w.N
+    R = B * Tq
+    f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)     # noqa: E731
+    w.route = route
+    if route == "tiled":                  # no [B, heads, Tq, S] probabilities: lse per attention, one delta workspace
+        att = lambda: dict(lse_sa=f(B, heads, Tq), lse_ca=f(B, heads, Tq))        # noqa: E731
+        w.delta = f(B, heads, Tq) if train else None
+    else:
+        att = lambda: dict(p_sa=f(B, heads, Tq, Tq), p_ca=f(B, heads, Tq, S))      # noqa: E731
+    w.tgt0 = torch.zeros(R, H, dtype=torch.float32, device=dev)           # tgt = zeros_like(query)
+    w.layers = [dict(sa_qkv=f(R, 3 * H), sa_o=f(R, H), t1_pre=f(R, H), t1=f(R, H), m1=f(R), r1=f(R), caq=f(R, H),
+                     cakv=f(N, 2 * H), ca_o=f(R, H), t2_pre=f(R, H), t2=f(R, H), m2=f(R), r2=f(R), ff1=f(R, 4 * H),
+                     t3_pre=f(R, H), t3=f(R, H), m3=f(R), r3=f(R), **att()) for _ in range(L)]
+    w.tgtF, w.mF, w.rF = f(R, H), f(R), f(R)
+    if train:
+        w.d_tgtF, w.d_t, w.d_mp = f(R, H), f(R, H), f(N, H)
+        w.glayers = [dict(t3pre=f(R, H), ff2=f(R, H), ff1=f(R, 4 * H), t2=f(R, H), t2pre=f(R, H), cap=f(R, H), cao=f(R, H),
+                          caq=f(R, H), cakv=f(N, 2 * H), caqin=f(R, H), t1pre=f(R, H), sap=f(R, H), sao=f(R, H),
+                          saqkv=f(R, 3 * H), sain=f(R, H)) for _ in range(L)]
+        w.drop_pool, w.drop = drop_pool({**own_drop_sizes, **decoder_drop_sizes(L, B, heads, H, R, Tq, S)}, dev)
+
+
+# ---- forward and backward -----------------------------------------------------------------------------------------------
+def decoder_forward(eng, w, qpos, qmod, mem, key_labels, drop):
+    """w.tgt0 through the layers and transformer.decoder.norm into w.tgtF.  q = k = tgt + query_pos in the self-attention,
+    q = tgt + query_pos against k = v = memory + pos in the cross-attention, whose keys key_labels == pad_idx mask."""
+    a, H, heads, dh, ws, B, S = eng.arena, eng.H, eng.heads, eng.dh, eng.ws, w.B, w.S
+    R = w.tgt0.shape[0]
+    Tq = R // B
+    dm = (lambda k: w.drop[k]) if drop else (lambda k: None)
+    dm2 = lambda k, cols: eng._dm2(dm(k), R, cols)         # noqa: E731
+    dsc = DROP_SCALE
+
+    def attend(q, k, v, c, at, Lk, l, **mask):
+        if w.route == "tiled":
+            ops.mha_tiled_fwd(q, k, v, c[at + "_o"], c["lse_" + at], B, heads, Tq, Lk, dh, drop_mask=dm(f"{at}_p{l}"),
+                              drop_scale=dsc, **mask)
+        else:
+            ops.mha_core_fwd(q, k, v, c["p_" + at], c[at + "_o"], B, heads, Tq, Lk, dh, drop_mask=dm(f"{at}_p{l}"),
+                             drop_scale=dsc, **mask)
+
+    pos = a.p("pos_embedding")[0, :S]
+    tgt = w.tgt0
+    for l in range(eng.L):
+        c, pl = w.layers[l], f"transformer.decoder.layers.{l}."
+        p = lambda n: a.p(pl + n)         # noqa: E731
+        ops.gemm(GEMM_NT, tgt, p("self_attn.in_proj_weight"), c["sa_qkv"], a_add=qpos, a_add_mod=qmod,
+                 bias=p("self_attn.in_proj_bias"), ws=ws)
+        attend(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c, "sa", Tq, l)
+        ops.gemm(GEMM_NT, c["sa_o"], p("self_attn.out_proj.weight"), c["t1_pre"], bias=p("self_attn.out_proj.bias"),
+                 drop_mask=dm2(f"d1_{l}", H), drop_scale=dsc, res1=None if l == 0 else tgt, ws=ws)
+        ops.layernorm_fwd(c["t1_pre"], p("norm1.weight"), p("norm1.bias"), c["t1"], c["m1"], c["r1"])
+        wi, bi = p("multihead_attn.in_proj_weight"), p("multihead_attn.in_proj_bias")
+        ops.gemm(GEMM_NT, c["t1"], wi[:H], c["caq"], a_add=qpos, a_add_mod=qmod, bias=bi[:H], ws=ws)
+        ops.gemm(GEMM_NT, mem, wi[H:], c["cakv"], a_add=pos, a_add_mod=S, bias=bi[H:], ws=ws)
+        attend(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c, "ca", S, l, key_labels=key_labels, pad_idx=eng.pad_idx)
+        ops.gemm(GEMM_NT, c["ca_o"], p("multihead_attn.out_proj.weight"), c["t2_pre"],
+                 bias=p("multihead_attn.out_proj.bias"), drop_mask=dm2(f"d2_{l}", H), drop_scale=dsc, res1=c["t1"], ws=ws)
+        ops.layernorm_fwd(c["t2_pre"], p("norm2.weight"), p("norm2.bias"), c["t2"], c["m2"], c["r2"])
+        ops.gemm(GEMM_NT, c["t2"], p("linear1.weight"), c["ff1"], bias=p("linear1.bias"), act=1,
+                 drop_mask=dm2(f"ff_{l}", 4 * H), drop_scale=dsc, ws=ws)
+        ops.gemm(GEMM_NT, c["ff1"], p("linear2.weight"), c["t3_pre"], bias=p("linear2.bias"),
+                 drop_mask=dm2(f"d3_{l}", H), drop_scale=dsc, res1=c["t2"], ws=ws)
+        ops.layernorm_fwd(c["t3_pre"], p("norm3.weight"), p("norm3.bias"), c["t3"], c["m3"], c["r3"])
+        tgt = c["t3"]
+    ops.layernorm_fwd(tgt, a.p("transformer.decoder.norm.weight"), a.p("transformer.decoder.norm.bias"), w.tgtF, w.mF, w.rF)
+
+
+def decoder_backward(eng, w, qpos, qmod, mem, key_labels, drop, g_qpos=None):
+    """Adjoint of decoder_forward from w.d_tgtF: every decoder parameter's gradient, the query position's (see g_qpos),
+    d (memory + pos) in w.d_mp and, from it, pos_embedding's gradient."""
+    a, H, heads, dh, ws, B, S, L = eng.arena, eng.H, eng.heads, eng.dh, eng.ws, w.B, w.S, eng.L
+    R = w.tgt0.shape[0]
+    Tq = R // B
+    dm = (lambda k, cols: w.drop[k].view(R, cols)) if drop else (lambda k, cols: None)
+    dmf = (lambda k: w.drop[k]) if drop else (lambda k: None)
+    dsc = DROP_SCALE
+    pos = a.p("pos_embedding")[0, :S]
+
+    def ln_bwd(dy, x, mean, rstd, name, dx, **kw):
+        gn, bn = name + ".weight", name + ".bias"
+        ops.layernorm_bwd(dy, x, mean, rstd, a.p(gn), a.p(bn), dx, a.g(gn), a.g(bn), ws=ws, **kw)
+
+    def wgrad(dy, x, gw, gb, **kw):
+        ops.gemm(GEMM_TN, dy, x, gw, bias_grad=gb, ws=ws, **kw)
+
+    def attend_bwd(q, k, v, c, at, d_o, dq, dk, dv, Lk, l, **mask):
+        if w.route == "tiled":            # (the probabilities are recomputed: the forward's key mask again)
+            ops.mha_tiled_bwd(q, k, v, c[at + "_o"], c["lse_" + at], d_o, w.delta, dq, dk, dv, B, heads, Tq, Lk, dh,
+                              drop_mask=dmf(f"{at}_p{l}"), drop_scale=dsc, **mask)
+        else:
+            ops.mha_core_bwd(q, k, v, c["p_" + at], d_o, dq, dk, dv, B, heads, Tq, Lk, dh, drop_mask=dmf(f"{at}_p{l}"),
+                             drop_scale=dsc)
+
+    ln_bwd(w.d_tgtF, w.layers[-1]["t3"], w.mF, w.rF, "transformer.decoder.norm", w.d_t)
+    dy, dy2 = w.d_t, None
+    for l in reversed(range(L)):
+        c, gl, pl = w.layers[l], w.glayers[l], f"transformer.decoder.layers.{l}."
+        p = lambda n: a.p(pl + n)         # noqa: E731
+        g = lambda n: a.g(pl + n)         # noqa: E731
+        tgt_in = w.tgt0 if l == 0 else w.layers[l - 1]["t3"]
+        ln_bwd(dy, c["t3_pre"], c["m3"], c["r3"], pl + "norm3", gl["t3pre"], dy2=dy2, dx2=gl["ff2"],
+               drop_mask=dm(f"d3_{l}", H), drop_scale=dsc)
+        wgrad(gl["ff2"], c["ff1"], g("linear2.weight"), g("linear2.bias"))
+        ops.gemm(GEMM_NN, gl["ff2"], p("linear2.weight"), gl["ff1"], drop_mask=dm(f"ff_{l}", 4 * H), drop_scale=dsc,
+                 aux=c["ff1"], mul=1, ws=ws)
+        wgrad(gl["ff1"], c["t2"], g("linear1.weight"), g("linear1.bias"))
+        ops.gemm(GEMM_NN, gl["ff1"], p("linear1.weight"), gl["t2"], res1=gl["t3pre"], ws=ws)
+        ln_bwd(gl["t2"], c["t2_pre"], c["m2"], c["r2"], pl + "norm2", gl["t2pre"], dx2=gl["cap"],
+               drop_mask=dm(f"d2_{l}", H), drop_scale=dsc)
+        wgrad(gl["cap"], c["ca_o"], g("multihead_attn.out_proj.weight"), g("multihead_attn.out_proj.bias"))
+        ops.gemm(GEMM_NN, gl["cap"], p("multihead_attn.out_proj.weight"), gl["cao"], ws=ws)
+        attend_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c, "ca", gl["cao"], gl["caq"], gl["cakv"][:, :H],
+                   gl["cakv"][:, H:], S, l, key_labels=key_labels, pad_idx=eng.pad_idx)
+        wi = p("multihead_attn.in_proj_weight")
+        gwi, gbi = g("multihead_attn.in_proj_weight"), g("multihead_attn.in_proj_bias")
+        wgrad(gl["cakv"], mem, gwi[H:], gbi[H:], b_add=pos, b_add_mod=S)
+        wgrad(gl["caq"], c["t1"], gwi[:H], gbi[:H], b_add=qpos, b_add_mod=qmod)
+        ops.gemm(GEMM_NN, gl["cakv"], wi[H:], w.d_mp, accumulate=(l != L - 1), ws=ws)         # d (memory + pos)
+        ops.gemm(GEMM_NN, gl["caq"], wi[:H], gl["caqin"], ws=ws)                              # d (t1 + query_pos)
+        ln_bwd(gl["caqin"], c["t1_pre"], c["m1"], c["r1"], pl + "norm1", gl["t1pre"], dy2=gl["t2pre"], dx2=gl["sap"],
+               drop_mask=dm(f"d1_{l}", H), drop_scale=dsc)
+        wgrad(gl["sap"], c["sa_o"], g("self_attn.out_proj.weight"), g("self_attn.out_proj.bias"))
+        ops.gemm(GEMM_NN, gl["sap"], p("self_attn.out_proj.weight"), gl["sao"], ws=ws)
+        attend_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c, "sa", gl["sao"],
+                   gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], Tq, l)
+        wgrad(gl["saqkv"], tgt_in, g("self_attn.in_proj_weight"), g("self_attn.in_proj_bias"), b_add=qpos, b_add_mod=qmod)
+        ops.gemm(GEMM_NN, gl["saqkv"], p("self_attn.in_proj_weight"), gl["sain"], ws=ws)      # d (tgt_in + query_pos)
+        # d query_pos += caqin + sain, top layer first
+        if g_qpos is not None:            # a parameter: the clips' column sums
+            ops.rowmod_sum(gl["caqin"], qmod, g_qpos, accumulate=(l != L - 1))
+            ops.rowmod_sum(gl["sain"], qmod, g_qpos, accumulate=True)
+        elif l == L - 1:                  # an activation: its gradient flows on into the engine's branch
+            ops.add_rowbcast(gl["caqin"], gl["sain"], R, w.d_qpos)
+        else:
+            ops.add_rowbcast(gl["caqin"], gl["sain"], R, w.d_qtmp)
+            ops.add_rowbcast(w.d_qpos, w.d_qtmp, R, w.d_qpos)
+        dy, dy2 = gl["sain"], gl["t1pre"]           # d t3 of layer l-1 = through the queries + the residual
+    pos_embedding_grad(eng, w)
+
+
+def pos_embedding_grad(eng, w):
+    """pos_embedding's gradient: the column sums over the clips of d (memory + pos) into its first S rows.  The gradient is
+    written, not accumulated, so the rows [S, mark) that a longer earlier batch wrote are zeroed (the reference's zero_grad()
+    zeroes them); eng.pos_grad_rows is that high-water mark."""
+    S, g = w.S, eng.arena.g("pos_embedding")
+    ops.rowmod_sum(w.d_mp, S, g[0, :S])
+    if S < eng.pos_grad_rows:
+        g[0, S:eng.pos_grad_rows].zero_()
+    eng.pos_grad_rows = max(eng.pos_grad_rows, S)
+
+
+# ---- the engines' common plumbing ---------------------------------------------------------------------------------------
+class ComposedEngine:
+    """Base of the three engines: the device scalars, the fc | fc_len head views, AdamW over the live prefix of the arena
+    and the graph capture of a whole step."""
+
+    def _init_step_state(self):
+        """(after self.arena, self.device, self.K and self.H are set)"""
+        dev = self.device
+        self.shapes, self.graphs = {}, {}
+        self.drop_seed = 0x5EED
+        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)        # device scalars: a captured graph sees updates
+        self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._lr_host = None
+        self.pos_grad_rows = 0            # high-water mark of the pos_embedding gradient rows written (pos_embedding_grad)
+        self.last = None
+        a, K, H = self.arena, self.K, self.H
+        o_w, o_b = a.offsets["fc.weight"][0], a.offsets["fc.bias"][0]
+        # the arena lays fc_len behind fc: [fc.weight ; fc_len.weight] = [K + 1, H] is one head product
+        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K
+        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
+        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
+        self.b_head = a.params[o_b:o_b + K + 1]
+        self.gb_head = a.grads[o_b:o_b + K + 1]
+
+    @staticmethod
+    def _dm2(m, rows, cols):
+        return None if m is None else m.view(rows, cols)
+
+    def set_lr(self, lr):
+        """True if the device scalar was written."""
+        if self._lr_host != float(lr):
+            self.lr_t.fill_(float(lr))
+            self._lr_host = float(lr)
+            return True
+        return False
+
+    @staticmethod
+    def _copy_in(w, d_seg, d_actdur):
+        """logit gradients handed to backward() by the caller (the autograd bridge) into the workspace's own buffers"""
+        if d_seg is not None and d_seg.data_ptr() != w.d_seg.data_ptr():
+            w.d_seg.copy_(d_seg)
+        if d_actdur is not None and d_actdur.data_ptr() != w.d_actdur.data_ptr():
+            w.d_actdur.copy_(d_actdur)
+
+    def _adamw_flat(self, weight_decay, betas, eps, grad_scale=1.0):
+        """One fused launch over the live prefix of the arena; the dead parameters are outside it."""
+        a, n = self.arena, self.arena.n_live
+        ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t, beta1=betas[0],
+                       beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+
+    def _replay(self, key, batch, run, more_state=()):
+        """run(bufs) -- a whole training step on the capture's own copies of `batch` -- replayed from a graph, one capture
+        per key.  What the warm-up step advances (the parameters, the moments, the counters and more_state) is put back
+        before the first replay."""
+        g = self.graphs.get(key)
+        if g is None:
+            self._shape(batch[0].shape[0], batch[0].shape[1], True)       # (admission and allocation outside the capture)
+            bufs = [t.clone() for t in batch]
+            state = (self.arena.params, self.arena.exp_avg, self.arena.exp_avg_sq, self.step_t, self.drop_offset) + more_state
+            snap = [t.clone() for t in state]
+            run(bufs)                                                     # warm-up: sizes the GEMM workspaces, sets attributes
+            graph = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graph):
+                out = run(bufs)
+            for dst, src in zip(state, snap):
+                dst.copy_(src)                                            # (undo the warm-up step; a capture runs nothing)
+            g = self.graphs[key] = dict(graph=graph, bufs=bufs, out=out)
+        for dst, src in zip(g["bufs"], batch):
+            dst.copy_(src)
+        g["graph"].replay()
+        return g["out"]

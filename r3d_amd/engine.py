@@ -265,16 +265,8 @@ class _Shape:
             if eng.plain:                                # per-frame modality-token partials (column sum = d modality_token)
                 self.t_tok = f(N, H)
             # dropout keep-masks (one Philox launch fills the whole pool)
-            sizes = dict(x0=2 * N * H)
-            for l in range(L):
-                sizes.update({f"sa_p{l}": B * heads * Q * Q, f"ca_p{l}": B * heads * Q * S, f"d1_{l}": BQ * H,
-                              f"d2_{l}": BQ * H, f"d3_{l}": BQ * H, f"ff_{l}": BQ * 4 * H})
-            tot = sum((v + 15) // 16 * 16 for v in sizes.values())
-            self.drop_pool = torch.ones(tot, dtype=torch.uint8, device=dev)
-            self.drop, o = {}, 0
-            for k, v in sizes.items():
-                self.drop[k] = self.drop_pool[o:o + v]
-                o += (v + 15) // 16 * 16
+            from .decoder_composed import decoder_drop_sizes, drop_pool          # (that module imports this one)
+            self.drop_pool, self.drop = drop_pool({"x0": 2 * N * H, **decoder_drop_sizes(L, B, heads, H, BQ, Q, S)}, dev)
 
 
 class FusionEngine:

@@ -21,6 +21,7 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
+from .decoder_composed import ComposedEngine, DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
 from .engine import ParamArena, DROP_P, check_hidden, max_clip_len
 
 LIVE_PREFIXES = ("input_embed.", "l3_attention.", "transformer.decoder.", "pos_embedding", "fc_seg.", "fc.", "fc_len.",
@@ -63,7 +64,7 @@ def check_l3_batch(B, S, H, heads, Q, max_pos_len, train):
 
 class _Shape:
     def __init__(self, eng, B, S, train):
-        dev, H, Q, K, L, heads, C = eng.device, eng.H, eng.Q, eng.K, eng.L, eng.heads, eng.C
+        dev, H, Q, K, C = eng.device, eng.H, eng.Q, eng.K, eng.C
         N, BQ = B * S, B * Q
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)     # noqa: E731
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)     # noqa: E731
@@ -71,12 +72,7 @@ class _Shape:
         self.rgb, self.mem = f(N, H), f(N, H)
         self.xqkv, self.xo, self.l3pre, self.l3 = f(N, 3 * H), f(N, H), f(N, H), f(N, H)
         self.qpos, self.l3log, self.seg = f(BQ, H), f(N, C), f(N, eng.Kseg)
-        self.tgt0 = z(BQ, H)
-        self.layers = [dict(sa_qkv=f(BQ, 3 * H), p_sa=f(B, heads, Q, Q), sa_o=f(BQ, H), t1_pre=f(BQ, H), t1=f(BQ, H), m1=f(BQ),
-                            r1=f(BQ), caq=f(BQ, H), cakv=f(N, 2 * H), p_ca=f(B, heads, Q, S), ca_o=f(BQ, H), t2_pre=f(BQ, H),
-                            t2=f(BQ, H), m2=f(BQ), r2=f(BQ), ff1=f(BQ, 4 * H), t3_pre=f(BQ, H), t3=f(BQ, H), m3=f(BQ), r3=f(BQ))
-                       for _ in range(L)]
-        self.tgtF, self.mF, self.rF = f(BQ, H), f(BQ), f(BQ)
+        decoder_buffers(self, eng, Q, "core", train, dict(pe_rgb=N * H))
         self.actdur = f(BQ, K + 1)
         # losses: loss3 = (seg, action, duration, their sum); l3 / lc device scalars; mix = (m, a, b, c, total)
         self.loss3, self.loss_l3, self.loss_lc, self.mix = f(4), f(1), f(1), f(5)
@@ -91,25 +87,11 @@ class _Shape:
         self.runs = [z(B * S, dt=torch.int32) for _ in range(3)] + [z(B, dt=torch.int32)]      # first, last, starts, count
         if train:
             self.d_actdur, self.d_seg, self.d_l3log = z(BQ, K + 1), f(N, eng.Kseg), f(N, C)
-            self.d_tgtF, self.d_t = f(BQ, H), f(BQ, H)
-            self.glayers = [dict(t3pre=f(BQ, H), ff2=f(BQ, H), ff1=f(BQ, 4 * H), t2=f(BQ, H), t2pre=f(BQ, H), cap=f(BQ, H),
-                                 cao=f(BQ, H), caq=f(BQ, H), cakv=f(N, 2 * H), caqin=f(BQ, H), t1pre=f(BQ, H), sap=f(BQ, H),
-                                 sao=f(BQ, H), saqkv=f(BQ, 3 * H), sain=f(BQ, H)) for _ in range(L)]
-            self.d_mp, self.d_mem, self.d_qpos, self.d_qtmp = f(N, H), f(N, H), f(BQ, H), f(BQ, H)
+            self.d_mem, self.d_qpos, self.d_qtmp = f(N, H), f(BQ, H), f(BQ, H)
             self.d_pool, self.d_l3, self.d_xo, self.d_xqkv, self.d_rgb_pre = f(N, H), f(N, H), f(N, H), f(N, 3 * H), f(N, H)
-            sizes = dict(pe_rgb=N * H)
-            for l in range(L):
-                sizes.update({f"sa_p{l}": B * heads * Q * Q, f"ca_p{l}": B * heads * Q * S, f"d1_{l}": BQ * H,
-                              f"d2_{l}": BQ * H, f"d3_{l}": BQ * H, f"ff_{l}": BQ * 4 * H})
-            tot = sum((v + 15) // 16 * 16 for v in sizes.values())
-            self.drop_pool = torch.ones(tot, dtype=torch.uint8, device=dev)
-            self.drop, o = {}, 0
-            for k, v in sizes.items():
-                self.drop[k] = self.drop_pool[o:o + v]
-                o += (v + 15) // 16 * 16
 
 
-class L3Engine:
+class L3Engine(ComposedEngine):
     def __init__(self, module, device):
         self.module = module
         self.device = torch.device(device)
@@ -130,24 +112,9 @@ class L3Engine:
         self.ws = ops.GemmWorkspace(self.device)
         self.dropout_enabled = bool(getattr(module, "r3d_dropout_enabled", True))
         self.erank_weight = 0.0
-        self.shapes = {}
-        self.drop_seed = 0x5EED
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.wf_t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._lr_host = self._wf_host = None
-        self.pos_grad_rows = 0
-        self.last = None
-        self.graphs = {}
-        a, K, H = self.arena, self.K, self.H
-        o_w = a.offsets["fc.weight"][0]
-        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        o_b = a.offsets["fc.bias"][0]
-        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K
-        self.b_head = a.params[o_b:o_b + K + 1]
-        self.gb_head = a.grads[o_b:o_b + K + 1]
+        self._wf_host = None
+        self._init_step_state()
 
     def _shape(self, B, S, train):
         key = (B, S, bool(train))
@@ -156,16 +123,12 @@ class L3Engine:
             self.shapes[key] = _Shape(self, B, S, train)
         return self.shapes[key]
 
-    @staticmethod
-    def _dm2(m, rows, cols):
-        return None if m is None else m.view(rows, cols)
-
     # ------------------------------------------------------------------------------------------------------
     def forward(self, feats, labels, mode="train", training=False, need_grad=True):
         """feats [B, S, D] f32, labels [B, S] int64 (train mode only: the decoder's key-padding mask).
         futr_unsupervised_temp3.py:72-143.  Returns views: l3 [B, S, query_num], seg [B, S, n_class], action [B, Q, K],
         duration [B, Q]."""
-        a, H, Q, K, heads, dh = self.arena, self.H, self.Q, self.K, self.heads, self.dh
+        a, Q, K, heads = self.arena, self.Q, self.K, self.heads
         B, S = feats.shape[0], feats.shape[1]
         N, BQ = B * S, B * Q
         assert feats.is_cuda and feats.dtype == torch.float32
@@ -175,7 +138,6 @@ class L3Engine:
         drop = training and need_grad and self.dropout_enabled
         if drop:
             ops.dropout_mask(w.drop_pool, DROP_P, self.drop_seed, self.drop_offset)
-        dsc = 1.0 / (1.0 - DROP_P)
         dm = (lambda k: w.drop[k]) if drop else (lambda k: None)
         key_labels = None
         if mode == "train":
@@ -184,7 +146,7 @@ class L3Engine:
         ws = self.ws
         # ---- memory: relu(x W^T + b) + pos_table, dropout (:87-93)
         ops.gemm(GEMM_NT, x, a.p("input_embed.weight"), w.rgb, bias=a.p("input_embed.bias"), act=1, ws=ws)
-        ops.posenc_fwd(w.rgb, self.pe, S, w.mem, drop_mask=dm("pe_rgb"), drop_scale=dsc)
+        ops.posenc_fwd(w.rgb, self.pe, S, w.mem, drop_mask=dm("pe_rgb"), drop_scale=DROP_SCALE)
         # ---- l3 branch: attention over the clips of each frame (:99-104), no mask, no dropout
         ops.gemm(GEMM_NT, w.mem, a.p("l3_attention.in_proj_weight"), w.xqkv, bias=a.p("l3_attention.in_proj_bias"), ws=ws)
         ops.xclip_fwd(w.xqkv, w.xo, B, S, heads)
@@ -194,35 +156,7 @@ class L3Engine:
         ops.gemm(GEMM_NT, w.l3, a.p("fc_l3.weight"), w.l3log, bias=a.p("fc_l3.bias"), ws=ws)         # (:139)
         ops.gemm(GEMM_NT, w.mem, a.p("fc_seg.weight"), w.seg, bias=a.p("fc_seg.bias"), ws=ws)        # (:134)
         # ---- decoder, post-norm: Q queries per clip, query_pos = w.qpos, memory + pos as keys and values
-        pos = a.p("pos_embedding")[0, :S]
-        tgt = w.tgt0
-        for l in range(self.L):
-            c, pl = w.layers[l], f"transformer.decoder.layers.{l}."
-            p = lambda n: a.p(pl + n)         # noqa: E731
-            ops.gemm(GEMM_NT, tgt, p("self_attn.in_proj_weight"), c["sa_qkv"], a_add=w.qpos, a_add_mod=BQ,
-                     bias=p("self_attn.in_proj_bias"), ws=ws)
-            ops.mha_core_fwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], c["sa_o"], B,
-                             heads, Q, Q, dh, drop_mask=dm(f"sa_p{l}"), drop_scale=dsc)
-            ops.gemm(GEMM_NT, c["sa_o"], p("self_attn.out_proj.weight"), c["t1_pre"], bias=p("self_attn.out_proj.bias"),
-                     drop_mask=self._dm2(dm(f"d1_{l}"), BQ, H), drop_scale=dsc, res1=None if l == 0 else tgt, ws=ws)
-            ops.layernorm_fwd(c["t1_pre"], p("norm1.weight"), p("norm1.bias"), c["t1"], c["m1"], c["r1"])
-            wi, bi = p("multihead_attn.in_proj_weight"), p("multihead_attn.in_proj_bias")
-            ops.gemm(GEMM_NT, c["t1"], wi[:H], c["caq"], a_add=w.qpos, a_add_mod=BQ, bias=bi[:H], ws=ws)
-            ops.gemm(GEMM_NT, w.mem, wi[H:], c["cakv"], a_add=pos, a_add_mod=S, bias=bi[H:], ws=ws)
-            ops.mha_core_fwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], c["ca_o"], B, heads, Q, S, dh,
-                             key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=dm(f"ca_p{l}"), drop_scale=dsc)
-            ops.gemm(GEMM_NT, c["ca_o"], p("multihead_attn.out_proj.weight"), c["t2_pre"],
-                     bias=p("multihead_attn.out_proj.bias"), drop_mask=self._dm2(dm(f"d2_{l}"), BQ, H), drop_scale=dsc,
-                     res1=c["t1"], ws=ws)
-            ops.layernorm_fwd(c["t2_pre"], p("norm2.weight"), p("norm2.bias"), c["t2"], c["m2"], c["r2"])
-            ops.gemm(GEMM_NT, c["t2"], p("linear1.weight"), c["ff1"], bias=p("linear1.bias"), act=1,
-                     drop_mask=self._dm2(dm(f"ff_{l}"), BQ, 4 * H), drop_scale=dsc, ws=ws)
-            ops.gemm(GEMM_NT, c["ff1"], p("linear2.weight"), c["t3_pre"], bias=p("linear2.bias"),
-                     drop_mask=self._dm2(dm(f"d3_{l}"), BQ, H), drop_scale=dsc, res1=c["t2"], ws=ws)
-            ops.layernorm_fwd(c["t3_pre"], p("norm3.weight"), p("norm3.bias"), c["t3"], c["m3"], c["r3"])
-            tgt = c["t3"]
-        ops.layernorm_fwd(tgt, a.p("transformer.decoder.norm.weight"), a.p("transformer.decoder.norm.bias"), w.tgtF, w.mF,
-                          w.rF)
+        decoder_forward(self, w, w.qpos, BQ, w.mem, key_labels, drop)
         ops.gemm(GEMM_NT, w.tgtF, self.w_head, w.actdur, bias=self.b_head, ws=ws)
         self.last = dict(w=w, x=x, drop=drop, mode=mode, key_labels=key_labels)
         return dict(l3=w.l3log.view(B, S, self.C), seg=w.seg.view(B, S, self.Kseg), action=w.actdur[:, :K].view(B, Q, K),
@@ -264,70 +198,17 @@ class L3Engine:
     def backward(self):
         """Adjoint of forward() from d_seg, d_actdur and d_l3log; gradients land in the grad arena (written, not accumulated)."""
         st = self.last
-        w, a, H, Q, K, heads, dh, ws = st["w"], self.arena, self.H, self.Q, self.K, self.heads, self.dh, self.ws
-        B, S, N, BQ = w.B, w.S, w.N, w.BQ
+        w, a, Q, heads, ws = st["w"], self.arena, self.Q, self.heads, self.ws
+        B, S, BQ = w.B, w.S, w.BQ
         drop = st["drop"]
-        dsc = 1.0 / (1.0 - DROP_P)
-        dm = (lambda k, r, c: w.drop[k].view(r, c)) if drop else (lambda k, r, c: None)
-        dmf = (lambda k: w.drop[k]) if drop else (lambda k: None)
-        pos = a.p("pos_embedding")[0, :S]
-
-        def ln_bwd(dy, x, mean, rstd, gname, bname, dx, **kw):
-            ops.layernorm_bwd(dy, x, mean, rstd, a.p(gname), a.p(bname), dx, a.g(gname), a.g(bname), ws=ws, **kw)
 
         def wgrad(dy, x, gw, gb, **kw):
             ops.gemm(GEMM_TN, dy, x, gw, bias_grad=gb, ws=ws, **kw)
 
-        # ---- heads, decoder.norm
+        # ---- heads, decoder
         wgrad(w.d_actdur, w.tgtF, self.gw_head, self.gb_head)
         ops.gemm(GEMM_NN, w.d_actdur, self.w_head, w.d_tgtF, ws=ws)
-        lastl = w.layers[-1]
-        ln_bwd(w.d_tgtF, lastl["t3"], w.mF, w.rF, "transformer.decoder.norm.weight", "transformer.decoder.norm.bias", w.d_t)
-        dy, dy2 = w.d_t, None
-        for l in reversed(range(self.L)):
-            c, gl, pl = w.layers[l], w.glayers[l], f"transformer.decoder.layers.{l}."
-            p = lambda n: a.p(pl + n)         # noqa: E731
-            g = lambda n: a.g(pl + n)         # noqa: E731
-            tgt_in = w.tgt0 if l == 0 else w.layers[l - 1]["t3"]
-            ln_bwd(dy, c["t3_pre"], c["m3"], c["r3"], pl + "norm3.weight", pl + "norm3.bias", gl["t3pre"], dy2=dy2,
-                   dx2=gl["ff2"], drop_mask=dm(f"d3_{l}", BQ, H), drop_scale=dsc)
-            wgrad(gl["ff2"], c["ff1"], g("linear2.weight"), g("linear2.bias"))
-            ops.gemm(GEMM_NN, gl["ff2"], p("linear2.weight"), gl["ff1"], drop_mask=dm(f"ff_{l}", BQ, 4 * H), drop_scale=dsc,
-                     aux=c["ff1"], mul=1, ws=ws)
-            wgrad(gl["ff1"], c["t2"], g("linear1.weight"), g("linear1.bias"))
-            ops.gemm(GEMM_NN, gl["ff1"], p("linear1.weight"), gl["t2"], res1=gl["t3pre"], ws=ws)
-            ln_bwd(gl["t2"], c["t2_pre"], c["m2"], c["r2"], pl + "norm2.weight", pl + "norm2.bias", gl["t2pre"],
-                   dx2=gl["cap"], drop_mask=dm(f"d2_{l}", BQ, H), drop_scale=dsc)
-            wgrad(gl["cap"], c["ca_o"], g("multihead_attn.out_proj.weight"), g("multihead_attn.out_proj.bias"))
-            ops.gemm(GEMM_NN, gl["cap"], p("multihead_attn.out_proj.weight"), gl["cao"], ws=ws)
-            ops.mha_core_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], gl["cao"], gl["caq"], gl["cakv"][:, :H],
-                             gl["cakv"][:, H:], B, heads, Q, S, dh, drop_mask=dmf(f"ca_p{l}"), drop_scale=dsc)
-            wi = p("multihead_attn.in_proj_weight")
-            gwi, gbi = g("multihead_attn.in_proj_weight"), g("multihead_attn.in_proj_bias")
-            wgrad(gl["cakv"], w.mem, gwi[H:], gbi[H:], b_add=pos, b_add_mod=S)
-            wgrad(gl["caq"], c["t1"], gwi[:H], gbi[:H], b_add=w.qpos, b_add_mod=BQ)
-            ops.gemm(GEMM_NN, gl["cakv"], wi[H:], w.d_mp, accumulate=(l != self.L - 1), ws=ws)     # d (memory + pos)
-            ops.gemm(GEMM_NN, gl["caq"], wi[:H], gl["caqin"], ws=ws)                              # d (t1 + query_pos)
-            ln_bwd(gl["caqin"], c["t1_pre"], c["m1"], c["r1"], pl + "norm1.weight", pl + "norm1.bias", gl["t1pre"],
-                   dy2=gl["t2pre"], dx2=gl["sap"], drop_mask=dm(f"d1_{l}", BQ, H), drop_scale=dsc)
-            wgrad(gl["sap"], c["sa_o"], g("self_attn.out_proj.weight"), g("self_attn.out_proj.bias"))
-            ops.gemm(GEMM_NN, gl["sap"], p("self_attn.out_proj.weight"), gl["sao"], ws=ws)
-            ops.mha_core_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], gl["sao"],
-                             gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], B, heads, Q, Q, dh,
-                             drop_mask=dmf(f"sa_p{l}"), drop_scale=dsc)
-            wgrad(gl["saqkv"], tgt_in, g("self_attn.in_proj_weight"), g("self_attn.in_proj_bias"), b_add=w.qpos, b_add_mod=BQ)
-            ops.gemm(GEMM_NN, gl["saqkv"], p("self_attn.in_proj_weight"), gl["sain"], ws=ws)      # d (tgt_in + query_pos)
-            if l == self.L - 1:                        # d query_pos += caqin + sain (the query is an activation)
-                ops.add_rowbcast(gl["caqin"], gl["sain"], BQ, w.d_qpos)
-            else:
-                ops.add_rowbcast(gl["caqin"], gl["sain"], BQ, w.d_qtmp)
-                ops.add_rowbcast(w.d_qpos, w.d_qtmp, BQ, w.d_qpos)
-            dy, dy2 = gl["sain"], gl["t1pre"]
-        # ---- learned positional embedding: column sums over the clips of d (memory + pos)
-        ops.rowmod_sum(w.d_mp, S, a.g("pos_embedding")[0, :S])
-        if S < self.pos_grad_rows:
-            a.g("pos_embedding")[0, S:self.pos_grad_rows].zero_()
-        self.pos_grad_rows = max(self.pos_grad_rows, S)
+        decoder_backward(self, w, w.qpos, BQ, w.mem, st["key_labels"], drop)      # (the query is an activation: w.d_qpos)
         # ---- d l3 = the pool's adjoint (decoder query) + fc_l3's input gradient
         ops.avgpool_rows_bwd(w.d_qpos, w.d_pool, B, S, Q)
         wgrad(w.d_l3log, w.l3, a.g("fc_l3.weight"), a.g("fc_l3.bias"))
@@ -341,24 +222,16 @@ class L3Engine:
         wgrad(w.d_seg, w.mem, a.g("fc_seg.weight"), a.g("fc_seg.bias"))
         ops.gemm(GEMM_NN, w.d_seg, a.p("fc_seg.weight"), w.d_mem, res1=w.d_mp, ws=ws)
         ops.gemm(GEMM_NN, w.d_xqkv, a.p("l3_attention.in_proj_weight"), w.d_mem, accumulate=True, ws=ws)
-        ops.posenc_bwd(w.d_mem, w.d_rgb_pre, drop_mask=dmf("pe_rgb"), drop_scale=dsc, gate=w.rgb)
+        ops.posenc_bwd(w.d_mem, w.d_rgb_pre, drop_mask=w.drop["pe_rgb"] if drop else None, drop_scale=DROP_SCALE, gate=w.rgb)
         wgrad(w.d_rgb_pre, st["x"], a.g("input_embed.weight"), a.g("input_embed.bias"))
 
     # ------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr):
-        if self._lr_host != float(lr):
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-
     def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, ticked=False):
         """One fused launch over the live prefix of the arena."""
-        a = self.arena
         self.set_lr(lr)
         if not ticked:
             ops.tick(self.step_t, self.drop_offset if (self.last and self.last["drop"]) else None)
-        n = a.n_live
-        ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t, beta1=betas[0],
-                       beta2=betas[1], eps=eps, weight_decay=weight_decay)
+        self._adamw_flat(weight_decay, betas, eps)
 
     def train_step(self, feats, past_label, target_dur, target, query_label, lr, weight_decay, wf, training=True,
                    betas=(0.9, 0.999), eps=1e-8, acc=None):
@@ -388,22 +261,5 @@ class L3Engine:
         key = (B, S, float(weight_decay), tuple(betas), float(eps), bool(training and self.dropout_enabled), acc is not None)
         self.set_lr(lr)
         self.set_wf(wf)
-        g = self.graphs.get(key)
-        if g is None:
-            self._shape(B, S, True)                                           # (admission and allocation outside the capture)
-            bufs = [t.clone() for t in (feats, past_label, target_dur, target, query_label)]
-            state = (self.arena.params, self.arena.exp_avg, self.arena.exp_avg_sq, self.step_t, self.drop_offset) + tuple(acc or ())
-            snap = [t.clone() for t in state]
-            run = lambda: self.train_step(*bufs, lr, weight_decay, wf, training, betas, eps, acc)      # noqa: E731
-            run()                                                             # warm-up: sizes the GEMM workspace, sets attributes
-            graph = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graph):
-                out = run()
-            for dst, src in zip(state, snap):
-                dst.copy_(src)                                                # (undo the warm-up step; a capture runs nothing)
-            g = self.graphs[key] = dict(graph=graph, bufs=bufs, out=out)
-        for dst, src in zip(g["bufs"], (feats, past_label, target_dur, target, query_label)):
-            dst.copy_(src)
-        g["graph"].replay()
-        return g["out"]
+        return self._replay(key, (feats, past_label, target_dur, target, query_label), lambda bufs: self.train_step(
+            *bufs, lr, weight_decay, wf, training, betas, eps, acc), tuple(acc or ()))

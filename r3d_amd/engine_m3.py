@@ -14,9 +14,10 @@ applies, split-K slabs left for the seam), then either
 cmfuser3.CMFuser3 makes over the 3N token rows: the qkv GEMM, r3d_attn3_fwd, proj + residual, norm2, fc1 with GELU (its
 pre-activation kept), fc2 with both residuals, fuser.norm, r3d_triple_mean_fwd.  Selection: the train-mode mask is a constant,
 computed once; eval mode runs three r3d_colabssum launches + r3d_token_select as CMFuser3.select does; `last_idx` keeps the
-selected indices readable.  Decoder, heads and losses are the composed launches FusionEngine._decoder_unfused and engine_l3
-use (mha_core_*, layernorm_*, r3d_losses_fwd_bwd); any number of decoder layers.  The backward mirrors the forward; weight
-gradients are GEMMs with column-sum epilogues; the depth weight gradient and AdamW follow engine_afft.
+selected indices readable.  The decoder is decoder_composed's (the launches FusionEngine._decoder_unfused makes: mha_core_*,
+layernorm_*; query_pos = the query_embed parameter), heads and losses r3d_losses_fwd_bwd; any number of decoder layers.
+The backward mirrors the forward; weight gradients are GEMMs with column-sum epilogues; the depth weight gradient and AdamW
+follow engine_afft.
 
 Rank penalty (erank_weight, erank_route) on the fused tokens [N = B S, H]: the ops / erank calls of
 FusionEngine._erank_forward / _erank_backward -- the in-LDS Jacobi where erank_fits, the blocked Jacobi on the orientation
@@ -32,6 +33,7 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
+from .decoder_composed import ComposedEngine, DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
 from .engine import (DROP_P, EXCLUDE_CLASS_IDX, ERANK_ROUTES, SEAM_MAX_H, ParamArena, check_hidden, check_erank_shape,
                      max_clip_len)
 
@@ -111,7 +113,7 @@ class _Shape:
     """Activation / gradient workspace for one (B, S, train) shape; rgb, dep, gaze and fused are the names rankstream reads."""
 
     def __init__(self, eng, B, S, train):
-        dev, H, Q, K, L, heads, G = eng.device, eng.H, eng.Q, eng.K, eng.L, eng.heads, eng.G
+        dev, H, Q, K, heads = eng.device, eng.H, eng.Q, eng.K, eng.heads
         N, BQ = B * S, B * Q
         R = 3 * N
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)     # noqa: E731
@@ -127,40 +129,21 @@ class _Shape:
         self.u, self.f1, self.x3 = f(R, 4 * H), f(R, 4 * H), f(R, H)
         self.y, self.mf, self.rf, self.fused = f(R, H), f(R), f(R), f(N, H)
         self.seg = f(N, K)
-        self.tgt0 = torch.zeros(BQ, H, dtype=torch.float32, device=dev)
-        self.layers = [dict(sa_qkv=f(BQ, 3 * H), p_sa=f(B, heads, Q, Q), sa_o=f(BQ, H), t1_pre=f(BQ, H), t1=f(BQ, H), m1=f(BQ),
-                            r1=f(BQ), caq=f(BQ, H), cakv=f(N, 2 * H), p_ca=f(B, heads, Q, S), ca_o=f(BQ, H), t2_pre=f(BQ, H),
-                            t2=f(BQ, H), m2=f(BQ), r2=f(BQ), ff1=f(BQ, 4 * H), t3_pre=f(BQ, H), t3=f(BQ, H), m3=f(BQ), r3=f(BQ))
-                       for _ in range(L)]
-        self.tgtF, self.mF, self.rF = f(BQ, H), f(BQ), f(BQ)
+        decoder_buffers(self, eng, Q, "core", train, dict(x0=R * H))
         self.actdur = f(BQ, K + 1)
         self.loss = torch.zeros(4, dtype=torch.float32, device=dev)
         self.counts = torch.zeros(4, dtype=torch.int64, device=dev)
         self.loss_ws = torch.zeros(ops.losses_ws_floats(B, S, Q), dtype=torch.float32, device=dev)
         if train:
             self.d_actdur, self.d_seg = torch.zeros(BQ, K + 1, dtype=torch.float32, device=dev), f(N, K)
-            self.d_tgtF, self.d_t = f(BQ, H), f(BQ, H)
-            self.glayers = [dict(t3pre=f(BQ, H), ff2=f(BQ, H), ff1=f(BQ, 4 * H), t2=f(BQ, H), t2pre=f(BQ, H), cap=f(BQ, H),
-                                 cao=f(BQ, H), caq=f(BQ, H), cakv=f(N, 2 * H), caqin=f(BQ, H), t1pre=f(BQ, H), sap=f(BQ, H),
-                                 sao=f(BQ, H), saqkv=f(BQ, 3 * H), sain=f(BQ, H)) for _ in range(L)]
-            self.d_mp, self.d_fused2 = f(N, H), f(N, H)
+            self.d_fused2 = f(N, H)
             self.d_y, self.d_x3, self.d_u, self.d_h2, self.d_x1 = f(R, H), f(R, H), f(R, 4 * H), f(R, H), f(R, H)
             self.d_att, self.d_qkv, self.d_h1, self.d_x0 = f(R, H), f(R, 3 * H), f(R, H), f(R, H)
             self.d_rgb, self.d_rgb_pre, self.d_dep, self.d_dep_pre, self.d_gz, self.d_gz_pre = (f(N, H) for _ in range(6))
             self.lnp_seam = dict(n1=f(2 * N * H), dep=f(2 * N * H), gz=f(2 * N * H))     # one (dgamma, dbeta) pair per frame
-            sizes = dict(x0=R * H)
-            for l in range(L):
-                sizes.update({f"sa_p{l}": B * heads * Q * Q, f"ca_p{l}": B * heads * Q * S, f"d1_{l}": BQ * H,
-                              f"d2_{l}": BQ * H, f"d3_{l}": BQ * H, f"ff_{l}": BQ * 4 * H})
-            tot = sum((v + 15) // 16 * 16 for v in sizes.values())
-            self.drop_pool = torch.ones(tot, dtype=torch.uint8, device=dev)
-            self.drop, o = {}, 0
-            for k, v in sizes.items():
-                self.drop[k] = self.drop_pool[o:o + v]
-                o += (v + 15) // 16 * 16
 
 
-class M3Engine:
+class M3Engine(ComposedEngine):
     def __init__(self, module, device):
         self.module = module
         self.device = torch.device(device)
@@ -186,28 +169,12 @@ class M3Engine:
         self._erank_weight, self._erank_route = 0.0, "jacobi"
         self.erank_fold = None
         self.erank_max_sweeps = 30
-        self.shapes = {}
-        self.drop_seed = 0x5EED
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._lr_host = None
         self._drop_ready = None                 # (the loop clears it; this engine never prefills a dropout pool)
-        self.pos_grad_rows = 0
         self.grad_hook = self.score_allreduce = self.dur_den = self.tp = None     # (one GPU: see refuse_data_parallel)
         self.rank_stream = None
         self.train_mask = None
         self.last_idx = None
-        self.last = None
-        self.graphs = {}
-        a, K, H = self.arena, self.K, self.H
-        o_w = a.offsets["fc.weight"][0]
-        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        o_b = a.offsets["fc.bias"][0]
-        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K
-        self.b_head = a.params[o_b:o_b + K + 1]
-        self.gb_head = a.grads[o_b:o_b + K + 1]
+        self._init_step_state()
 
     def refuse_data_parallel(self):
         """parallel.DataParallelStep asks this of an engine before it hooks into it: this one runs on one GPU"""
@@ -253,19 +220,15 @@ class M3Engine:
             self.train_mask = (idx, mask)
         return self.train_mask
 
-    @staticmethod
-    def _dm2(m, rows, cols):
-        return None if m is None else m.view(rows, cols)
-
     # ------------------------------------------------------------------------------------------------------
     def forward(self, feats, depth, labels, mode="train", training=False, need_grad=True, gaze=None):
         """feats [B,S,D] f32, depth [B,S,...] f32 (flattened to [N,P]), gaze [B,S,gaze_dim] f32, labels [B,S] int64 (train
         mode: the decoder's key padding mask).  Returns views into the workspace: seg [B,S,K], action [B,Q,K], duration [B,Q]."""
         if gaze is None:
             raise ValueError("the three-modality model needs the gaze track: forward(..., gaze=[B, S, gaze_dim])")
-        a, H, Q, K, heads, dh, G = self.arena, self.H, self.Q, self.K, self.heads, self.dh, self.G
+        a, H, Q, K, heads, G = self.arena, self.H, self.Q, self.K, self.heads, self.G
         B, S = feats.shape[0], feats.shape[1]
-        N, BQ, R = B * S, B * Q, 3 * B * S
+        N, R = B * S, 3 * B * S
         assert feats.is_cuda and depth.is_cuda and gaze.is_cuda
         assert feats.dtype == torch.float32 and depth.dtype == torch.float32 and gaze.dtype == torch.float32
         x_rgb, x_dep, x_gz = feats.reshape(N, -1), depth.reshape(N, -1), gaze.reshape(N, -1)
@@ -275,7 +238,7 @@ class M3Engine:
         drop = bool(training and need_grad and self.dropout_enabled)
         if drop:
             ops.dropout_mask(w.drop_pool, DROP_P, self.drop_seed, self.drop_offset)
-        dsc = 1.0 / (1.0 - DROP_P)
+        dsc = DROP_SCALE
         dm = (lambda k: w.drop[k]) if drop else (lambda k: None)
         key_labels = None
         if mode == "train":
@@ -347,35 +310,7 @@ class M3Engine:
             self._erank_forward(w)
         # ---- segmentation head (:228-232) and the decoder (memory = fused, encoder bypassed), post-norm
         ops.gemm(GEMM_NT, w.fused, p("fc_seg.weight"), w.seg, bias=p("fc_seg.bias"), ws=ws)
-        qpos = p("query_embed.weight")
-        pos = p("pos_embedding")[0, :S]
-        tgt = w.tgt0
-        for l in range(self.L):
-            c, pl = w.layers[l], f"transformer.decoder.layers.{l}."
-            q = lambda n: a.p(pl + n)         # noqa: E731
-            ops.gemm(GEMM_NT, tgt, q("self_attn.in_proj_weight"), c["sa_qkv"], a_add=qpos, a_add_mod=Q,
-                     bias=q("self_attn.in_proj_bias"), ws=ws)
-            ops.mha_core_fwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], c["sa_o"], B,
-                             heads, Q, Q, dh, drop_mask=dm(f"sa_p{l}"), drop_scale=dsc)
-            ops.gemm(GEMM_NT, c["sa_o"], q("self_attn.out_proj.weight"), c["t1_pre"], bias=q("self_attn.out_proj.bias"),
-                     drop_mask=self._dm2(dm(f"d1_{l}"), BQ, H), drop_scale=dsc, res1=None if l == 0 else tgt, ws=ws)
-            ops.layernorm_fwd(c["t1_pre"], q("norm1.weight"), q("norm1.bias"), c["t1"], c["m1"], c["r1"])
-            wi, bi = q("multihead_attn.in_proj_weight"), q("multihead_attn.in_proj_bias")
-            ops.gemm(GEMM_NT, c["t1"], wi[:H], c["caq"], a_add=qpos, a_add_mod=Q, bias=bi[:H], ws=ws)
-            ops.gemm(GEMM_NT, w.fused, wi[H:], c["cakv"], a_add=pos, a_add_mod=S, bias=bi[H:], ws=ws)
-            ops.mha_core_fwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], c["ca_o"], B, heads, Q, S, dh,
-                             key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=dm(f"ca_p{l}"), drop_scale=dsc)
-            ops.gemm(GEMM_NT, c["ca_o"], q("multihead_attn.out_proj.weight"), c["t2_pre"],
-                     bias=q("multihead_attn.out_proj.bias"), drop_mask=self._dm2(dm(f"d2_{l}"), BQ, H), drop_scale=dsc,
-                     res1=c["t1"], ws=ws)
-            ops.layernorm_fwd(c["t2_pre"], q("norm2.weight"), q("norm2.bias"), c["t2"], c["m2"], c["r2"])
-            ops.gemm(GEMM_NT, c["t2"], q("linear1.weight"), c["ff1"], bias=q("linear1.bias"), act=1,
-                     drop_mask=self._dm2(dm(f"ff_{l}"), BQ, 4 * H), drop_scale=dsc, ws=ws)
-            ops.gemm(GEMM_NT, c["ff1"], q("linear2.weight"), c["t3_pre"], bias=q("linear2.bias"),
-                     drop_mask=self._dm2(dm(f"d3_{l}"), BQ, H), drop_scale=dsc, res1=c["t2"], ws=ws)
-            ops.layernorm_fwd(c["t3_pre"], q("norm3.weight"), q("norm3.bias"), c["t3"], c["m3"], c["r3"])
-            tgt = c["t3"]
-        ops.layernorm_fwd(tgt, p("transformer.decoder.norm.weight"), p("transformer.decoder.norm.bias"), w.tgtF, w.mF, w.rF)
+        decoder_forward(self, w, p("query_embed.weight"), Q, w.fused, key_labels, drop)       # (query_pos: a parameter)
         ops.gemm(GEMM_NT, w.tgtF, self.w_head, w.actdur, bias=self.b_head, ws=ws)
         self.last = dict(w=w, x_rgb=x_rgb, x_dep=x_dep, x_gz=x_gz, mask=mask, idx=idx, drop=drop, mode=mode, seam=seam,
                          erank=er)
@@ -462,19 +397,14 @@ class M3Engine:
     def backward_main(self, d_seg=None, d_actdur=None):
         """Everything of the backward except depth_projection.weight."""
         st = self.last
-        w, a, H, Q, K, heads, dh, ws = st["w"], self.arena, self.H, self.Q, self.K, self.heads, self.dh, self.ws
-        B, S, N, BQ, R = w.B, w.S, w.N, w.BQ, w.R
+        w, a, H, heads, ws = st["w"], self.arena, self.H, self.heads, self.ws
+        N, R = w.N, w.R
         assert hasattr(w, "d_actdur"), "backward() needs a forward with need_grad=True"
-        if d_seg is not None and d_seg.data_ptr() != w.d_seg.data_ptr():
-            w.d_seg.copy_(d_seg)
-        if d_actdur is not None and d_actdur.data_ptr() != w.d_actdur.data_ptr():
-            w.d_actdur.copy_(d_actdur)
+        self._copy_in(w, d_seg, d_actdur)
         drop = st["drop"]
-        dsc = 1.0 / (1.0 - DROP_P)
+        dsc = DROP_SCALE
         dm = (lambda k, r, c: w.drop[k].view(r, c)) if drop else (lambda k, r, c: None)
         dmf = (lambda k: w.drop[k]) if drop else (lambda k: None)
-        qpos = a.p("query_embed.weight")
-        pos = a.p("pos_embedding")[0, :S]
         pre = "fuser.blocks.0."
 
         def ln_bwd(dy, x, mean, rstd, gname, bname, dx, **kw):
@@ -483,55 +413,10 @@ class M3Engine:
         def wgrad(dy, x, gw, gb, **kw):
             ops.gemm(GEMM_TN, dy, x, gw, bias_grad=gb, ws=ws, **kw)
 
-        # ---- heads, decoder.norm
+        # ---- heads, decoder (query_embed's gradient: the clips' column sums of the query-position gradients)
         wgrad(w.d_actdur, w.tgtF, self.gw_head, self.gb_head)
         ops.gemm(GEMM_NN, w.d_actdur, self.w_head, w.d_tgtF, ws=ws)
-        ln_bwd(w.d_tgtF, w.layers[-1]["t3"], w.mF, w.rF, "transformer.decoder.norm.weight", "transformer.decoder.norm.bias",
-               w.d_t)
-        g_qe = a.g("query_embed.weight")
-        dy, dy2 = w.d_t, None
-        for l in reversed(range(self.L)):
-            c, gl, pl = w.layers[l], w.glayers[l], f"transformer.decoder.layers.{l}."
-            p = lambda n: a.p(pl + n)         # noqa: E731
-            g = lambda n: a.g(pl + n)         # noqa: E731
-            tgt_in = w.tgt0 if l == 0 else w.layers[l - 1]["t3"]
-            ln_bwd(dy, c["t3_pre"], c["m3"], c["r3"], pl + "norm3.weight", pl + "norm3.bias", gl["t3pre"], dy2=dy2,
-                   dx2=gl["ff2"], drop_mask=dm(f"d3_{l}", BQ, H), drop_scale=dsc)
-            wgrad(gl["ff2"], c["ff1"], g("linear2.weight"), g("linear2.bias"))
-            ops.gemm(GEMM_NN, gl["ff2"], p("linear2.weight"), gl["ff1"], drop_mask=dm(f"ff_{l}", BQ, 4 * H), drop_scale=dsc,
-                     aux=c["ff1"], mul=1, ws=ws)
-            wgrad(gl["ff1"], c["t2"], g("linear1.weight"), g("linear1.bias"))
-            ops.gemm(GEMM_NN, gl["ff1"], p("linear1.weight"), gl["t2"], res1=gl["t3pre"], ws=ws)
-            ln_bwd(gl["t2"], c["t2_pre"], c["m2"], c["r2"], pl + "norm2.weight", pl + "norm2.bias", gl["t2pre"],
-                   dx2=gl["cap"], drop_mask=dm(f"d2_{l}", BQ, H), drop_scale=dsc)
-            wgrad(gl["cap"], c["ca_o"], g("multihead_attn.out_proj.weight"), g("multihead_attn.out_proj.bias"))
-            ops.gemm(GEMM_NN, gl["cap"], p("multihead_attn.out_proj.weight"), gl["cao"], ws=ws)
-            ops.mha_core_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], gl["cao"], gl["caq"], gl["cakv"][:, :H],
-                             gl["cakv"][:, H:], B, heads, Q, S, dh, drop_mask=dmf(f"ca_p{l}"), drop_scale=dsc)
-            wi = p("multihead_attn.in_proj_weight")
-            gwi, gbi = g("multihead_attn.in_proj_weight"), g("multihead_attn.in_proj_bias")
-            wgrad(gl["cakv"], w.fused, gwi[H:], gbi[H:], b_add=pos, b_add_mod=S)
-            wgrad(gl["caq"], c["t1"], gwi[:H], gbi[:H], b_add=qpos, b_add_mod=Q)
-            ops.gemm(GEMM_NN, gl["cakv"], wi[H:], w.d_mp, accumulate=(l != self.L - 1), ws=ws)     # d (memory + pos)
-            ops.gemm(GEMM_NN, gl["caq"], wi[:H], gl["caqin"], ws=ws)                              # d (t1 + query_pos)
-            ln_bwd(gl["caqin"], c["t1_pre"], c["m1"], c["r1"], pl + "norm1.weight", pl + "norm1.bias", gl["t1pre"],
-                   dy2=gl["t2pre"], dx2=gl["sap"], drop_mask=dm(f"d1_{l}", BQ, H), drop_scale=dsc)
-            wgrad(gl["sap"], c["sa_o"], g("self_attn.out_proj.weight"), g("self_attn.out_proj.bias"))
-            ops.gemm(GEMM_NN, gl["sap"], p("self_attn.out_proj.weight"), gl["sao"], ws=ws)
-            ops.mha_core_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], gl["sao"],
-                             gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], B, heads, Q, Q, dh,
-                             drop_mask=dmf(f"sa_p{l}"), drop_scale=dsc)
-            wgrad(gl["saqkv"], tgt_in, g("self_attn.in_proj_weight"), g("self_attn.in_proj_bias"), b_add=qpos, b_add_mod=Q)
-            ops.gemm(GEMM_NN, gl["saqkv"], p("self_attn.in_proj_weight"), gl["sain"], ws=ws)      # d (tgt_in + query_pos)
-            # query_embed: the clips' column sums of both query-position gradients, top layer first
-            ops.rowmod_sum(gl["caqin"], Q, g_qe, accumulate=(l != self.L - 1))
-            ops.rowmod_sum(gl["sain"], Q, g_qe, accumulate=True)
-            dy, dy2 = gl["sain"], gl["t1pre"]
-        # ---- learned positional embedding: column sums over the clips of d (memory + pos); rows past S stay zero
-        ops.rowmod_sum(w.d_mp, S, a.g("pos_embedding")[0, :S])
-        if S < self.pos_grad_rows:
-            a.g("pos_embedding")[0, S:self.pos_grad_rows].zero_()
-        self.pos_grad_rows = max(self.pos_grad_rows, S)
+        decoder_backward(self, w, a.p("query_embed.weight"), self.Q, w.fused, None, drop, a.g("query_embed.weight"))
         # ---- d fused = cross-attention K/V + segmentation head (+ the rank penalty)
         wgrad(w.d_seg, w.fused, a.g("fc_seg.weight"), a.g("fc_seg.bias"))
         ops.gemm(GEMM_NN, w.d_seg, a.p("fc_seg.weight"), w.d_fused2, res1=w.d_mp, ws=ws)
@@ -585,26 +470,16 @@ class M3Engine:
                  prec=self.depth_prec)
 
     # ------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr):
-        if self._lr_host != float(lr):          # lr lives in device memory so a captured graph sees scheduler updates
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-            return True
-        return False
-
     def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
               skip_depth=False, prefill_dropout=False, before_flat=None):
         """One fused launch over the live prefix of the arena; the dead parameters are outside it.  ticked: losses(tick=True)
         already advanced the counters.  (prefill_dropout is accepted for the loop's calling convention; every forward of this
         engine generates its own masks.)"""
         assert not skip_depth and before_flat is None
-        a = self.arena
         self.set_lr(lr)
         if not ticked:
             ops.tick(self.step_t, self.drop_offset if tick_dropout else None)
-        n = a.n_live
-        ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t, beta1=betas[0],
-                       beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+        self._adamw_flat(weight_decay, betas, eps, grad_scale)
 
     def train_step(self, feats, depth, past_label, target_dur, target, lr, weight_decay, training=True, gaze=None,
                    betas=(0.9, 0.999), eps=1e-8):
@@ -628,23 +503,5 @@ class M3Engine:
                bool(training and self.dropout_enabled), self._erank_weight, self._erank_route, self.use_seam,
                max(self.pos_grad_rows, S))
         self.set_lr(lr)
-        g = self.graphs.get(key)
-        batch = (feats, depth, past_label, target_dur, target, gaze)
-        if g is None:
-            self._shape(B, S, True)                                           # (admission and allocation outside the capture)
-            bufs = [t.clone() for t in batch]
-            state = (self.arena.params, self.arena.exp_avg, self.arena.exp_avg_sq, self.step_t, self.drop_offset)
-            snap = [t.clone() for t in state]
-            run = lambda: self.train_step(*bufs[:5], lr, weight_decay, training, gaze=bufs[5], betas=betas, eps=eps)  # noqa: E731
-            run()                                                             # warm-up: sizes the GEMM workspaces, sets attributes
-            graph = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graph):
-                out = run()
-            for dst, src in zip(state, snap):
-                dst.copy_(src)                                                # (undo the warm-up step; a capture runs nothing)
-            g = self.graphs[key] = dict(graph=graph, bufs=bufs, out=out)
-        for dst, src in zip(g["bufs"], batch):
-            dst.copy_(src)
-        g["graph"].replay()
-        return g["out"]
+        return self._replay(key, (feats, depth, past_label, target_dur, target, gaze), lambda bufs: self.train_step(
+            *bufs[:5], lr, weight_decay, training, gaze=bufs[5], betas=betas, eps=eps))
