@@ -766,6 +766,40 @@ typedef struct r3d_clip_collate_job {
 } r3d_clip_collate_job;
 int r3d_clip_collate(const r3d_clip_collate_job* job, void* stream);
 
+/* The same launch over a LIST of tracks (r3d_amd/clipcache.py: a layout), for batches that are not the five tensors above: one
+ * launch writes tracks[0 .. n_tracks) in that order.  Track t, with item = items[b] and o = off[item]:
+ *   R3D_CLIP_FRAMES_F32  out fp32 [B, S, width]  row (b, s) = src[ids[o + s]] (src: a pool of `rows` rows of `width` floats)
+ *   R3D_CLIP_WORDS_I64   out int64 [B, S]        src[o + s]                   (src: a table of `rows` words; width = 1)
+ *   R3D_CLIP_WORDS_F32   out fp32 [B, S]         src[o + s]
+ * for s < off[item + 1] - o; every other element of `out` is written with `pad` (cast to float for the fp32 kinds) by the same
+ * launch.  off: CSR of n_items + 1 entries; tracks may share one (two word tracks of one length).  An item id outside
+ * [0, n_items), a pool id outside [0, rows) or a word index outside [0, rows) reads nothing and yields padding.
+ * Frame rows of R3D_CLIP_WIDE_ROW (256) floats or more take r3d_clip_collate's mapping (one workgroup per destination row and
+ * 16-KiB chunk; 16-byte loads when width % 4 == 0 and src / out are 16-byte aligned, dword loads otherwise).  Narrower rows and
+ * all word tracks are packed: a workgroup writes 4096 consecutive elements of `out`, element e of a frame track being column
+ * e % width of row e / width, so a track of 8-byte rows costs a workgroup per 16 KiB, not per row.  The packed workgroups
+ * lead the grid (their dependent loads run under the wide rows' traffic); the outputs keep the tracks' order.
+ * B = 0, S = 0 and n_tracks = 0 are legal and enqueue nothing for that part.  R3D_EINVAL, before anything is enqueued: n_tracks
+ * outside [0, R3D_CLIP_MAX_TRACKS], an unknown kind, a negative B / n_items / S / rows, and on a track with B S > 0: width <= 0
+ * (or != 1 on a word track), a NULL items / off / out, or with rows > 0 a NULL src (or ids, for frames).
+ * Enqueue only (capturable), no atomics, all row arithmetic 64-bit. */
+#define R3D_CLIP_MAX_TRACKS 8
+#define R3D_CLIP_WIDE_ROW 256
+enum { R3D_CLIP_FRAMES_F32 = 0, R3D_CLIP_WORDS_I64 = 1, R3D_CLIP_WORDS_F32 = 2 };
+typedef struct r3d_clip_track {
+    int32_t kind, reserved;
+    const void* src; int64_t rows, width;
+    const int64_t* off; const int64_t* ids;     /* ids: frame tracks only */
+    int64_t S, pad;
+    void* out;
+} r3d_clip_track;
+typedef struct r3d_clip_tracks_job {
+    const int64_t* items; int64_t B, n_items;
+    int32_t n_tracks, reserved;
+    r3d_clip_track tracks[R3D_CLIP_MAX_TRACKS];
+} r3d_clip_tracks_job;
+int r3d_clip_collate_tracks(const r3d_clip_tracks_job* job, void* stream);
+
 /* ---- bidirectional LSTM layer (model/rnn.py:20,93: nn.LSTM(H, H/2, num_layers=2, bidirectional=True, batch_first=True))
  * The recurrence of one layer, both directions in one launch (one workgroup per clip and direction, W_hh in registers).
  * h = H / 2; rows are b-major (row = b * S + t); direction d (0 forward, 1 reverse) owns columns [4h d, 4h d + 4h) of the

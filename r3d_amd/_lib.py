@@ -162,6 +162,23 @@ class ClipCollateJob(C.Structure):
                 [(n, C.c_void_p) for n in "features depth past_label trans_future_dur trans_future_target".split()])
 
 
+CLIP_MAX_TRACKS = 8                     # R3D_CLIP_MAX_TRACKS
+CLIP_WIDE_ROW = 256                     # R3D_CLIP_WIDE_ROW
+CLIP_FRAMES_F32, CLIP_WORDS_I64, CLIP_WORDS_F32 = 0, 1, 2
+
+
+class ClipTrack(C.Structure):
+    """struct r3d_clip_track"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("src", C.c_void_p), ("rows", C.c_int64), ("width", C.c_int64),
+                ("off", C.c_void_p), ("ids", C.c_void_p), ("S", C.c_int64), ("pad", C.c_int64), ("out", C.c_void_p)]
+
+
+class ClipTracksJob(C.Structure):
+    """struct r3d_clip_tracks_job"""
+    _fields_ = [("items", C.c_void_p), ("B", C.c_int64), ("n_items", C.c_int64), ("n_tracks", C.c_int32),
+                ("reserved", C.c_int32), ("tracks", ClipTrack * CLIP_MAX_TRACKS)]
+
+
 class AfftHeadArgs(C.Structure):
     """struct r3d_afft_head_args"""
     _fields_ = [("fused", C.c_void_p), ("ld_fused", C.c_int32), ("w_head", C.c_void_p), ("b_head", C.c_void_p),
@@ -298,6 +315,7 @@ _SIGNATURES = {
     "r3d_erank_vt_polish": ([_P, _P, _P, _L, _P], C.c_int),
     "r3d_erank_plan": ([_I, _I, _I, _I, _P], C.c_int),
     "r3d_clip_collate": ([C.POINTER(ClipCollateJob), _P], C.c_int),
+    "r3d_clip_collate_tracks": ([C.POINTER(ClipTracksJob), _P], C.c_int),
     "r3d_losses_fwd_bwd_kseg": ([_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _I, _P, _I,
                                  _P, _I, _P, _P, _P, _P, _P, _P], C.c_int),
     "r3d_lstm_supported": ([_I], C.c_int),

@@ -192,10 +192,12 @@ class InputPrefetcher:
     """Wraps any iterable of the 5-tuple batches of BaseDataset.my_collate (basedataset_darai_depth.py:185-206) and keeps
     the NEXT batch on the device while the current step runs: pinned staging buffers + async copies on a side stream.
     The reference moves every batch synchronously inside the step (train_proposed_depth.py:132-137): 25.7 MB of depth
-    per step at the bench shape, 0.4 ms over PCIe -- longer than the whole HIP step."""
+    per step at the bench shape, 0.4 ms over PCIe -- longer than the whole HIP step.
+    long_at: the positions of the int64 label tensors in a batch -- (2, 4) for that 5-tuple and with a gaze track appended,
+    (1, 3, 4) for [features, past_label, trans_future_dur, trans_future_target, query_label]."""
 
-    def __init__(self, loader, device):
-        self.loader, self.device = loader, torch.device(device)
+    def __init__(self, loader, device, long_at=(2, 4)):
+        self.loader, self.device, self.long_at = loader, torch.device(device), tuple(long_at)
         self.stream = torch.cuda.Stream(self.device)
 
     def _stage(self, data):
@@ -205,7 +207,7 @@ class InputPrefetcher:
         with torch.cuda.stream(self.stream):
             for i, t in enumerate(data):
                 t = torch.as_tensor(t)
-                if i in (2, 4):
+                if i in self.long_at:
                     t = t.long()                                    # labels: float for NTU / UTKinect (cast at utils.py:365)
                 elif t.dtype != torch.float32:
                     t = t.float()
