@@ -1,6 +1,6 @@
 """The post-norm transformer decoder (reference transformer.py:281-330) composed launch by launch from ops.gemm, ops.mha_* and
-ops.layernorm_*, and the engine plumbing around it, shared by the query engines engine_unsup, engine_l3 and engine_m3 (the
-token-fusion engine's decoder is interleaved with streams, chain kernels and deferred tails: engine.py keeps its own).
+ops.layernorm_*, shared by the query engines engine_unsup, engine_l3 and engine_m3 (the token-fusion engine's decoder is
+interleaved with streams, chain kernels and deferred tails: engine.py keeps its own; its dropout pool is laid out here too).
 
 One decoder serves the three: `rows` query rows (B clips x Tq queries) attend to themselves and to the B x S rows of `mem`
 (+ pos_embedding[:S]).  What differs comes in as arguments:
@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .engine import DROP_P
+from .engine_base import DROP_P
 
 DROP_SCALE = 1.0 / (1.0 - DROP_P)
 
@@ -183,90 +183,4 @@ def decoder_backward(eng, w, qpos, qmod, mem, key_labels, drop, g_qpos=None):
             ops.add_rowbcast(gl["caqin"], gl["sain"], R, w.d_qtmp)
             ops.add_rowbcast(w.d_qpos, w.d_qtmp, R, w.d_qpos)
         dy, dy2 = gl["sain"], gl["t1pre"]           # d t3 of layer l-1 = through the queries + the residual
-    pos_embedding_grad(eng, w)
-
-
-def pos_embedding_grad(eng, w):
-    """pos_embedding's gradient: the column sums over the clips of d (memory + pos) into its first S rows.  The gradient is
-    written, not accumulated, so the rows [S, mark) that a longer earlier batch wrote are zeroed (the reference's zero_grad()
-    zeroes them); eng.pos_grad_rows is that high-water mark."""
-    S, g = w.S, eng.arena.g("pos_embedding")
-    ops.rowmod_sum(w.d_mp, S, g[0, :S])
-    if S < eng.pos_grad_rows:
-        g[0, S:eng.pos_grad_rows].zero_()
-    eng.pos_grad_rows = max(eng.pos_grad_rows, S)
-
-
-# ---- the engines' common plumbing ---------------------------------------------------------------------------------------
-class ComposedEngine:
-    """Base of the three engines: the device scalars, the fc | fc_len head views, AdamW over the live prefix of the arena
-    and the graph capture of a whole step."""
-
-    def _init_step_state(self):
-        """(after self.arena, self.device, self.K and self.H are set)"""
-        dev = self.device
-        self.shapes, self.graphs = {}, {}
-        self.drop_seed = 0x5EED
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)        # device scalars: a captured graph sees updates
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._lr_host = None
-        self.pos_grad_rows = 0            # high-water mark of the pos_embedding gradient rows written (pos_embedding_grad)
-        self.last = None
-        a, K, H = self.arena, self.K, self.H
-        o_w, o_b = a.offsets["fc.weight"][0], a.offsets["fc.bias"][0]
-        # the arena lays fc_len behind fc: [fc.weight ; fc_len.weight] = [K + 1, H] is one head product
-        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K
-        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.b_head = a.params[o_b:o_b + K + 1]
-        self.gb_head = a.grads[o_b:o_b + K + 1]
-
-    @staticmethod
-    def _dm2(m, rows, cols):
-        return None if m is None else m.view(rows, cols)
-
-    def set_lr(self, lr):
-        """True if the device scalar was written."""
-        if self._lr_host != float(lr):
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-            return True
-        return False
-
-    @staticmethod
-    def _copy_in(w, d_seg, d_actdur):
-        """logit gradients handed to backward() by the caller (the autograd bridge) into the workspace's own buffers"""
-        if d_seg is not None and d_seg.data_ptr() != w.d_seg.data_ptr():
-            w.d_seg.copy_(d_seg)
-        if d_actdur is not None and d_actdur.data_ptr() != w.d_actdur.data_ptr():
-            w.d_actdur.copy_(d_actdur)
-
-    def _adamw_flat(self, weight_decay, betas, eps, grad_scale=1.0):
-        """One fused launch over the live prefix of the arena; the dead parameters are outside it."""
-        a, n = self.arena, self.arena.n_live
-        ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t, beta1=betas[0],
-                       beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
-
-    def _replay(self, key, batch, run, more_state=()):
-        """run(bufs) -- a whole training step on the capture's own copies of `batch` -- replayed from a graph, one capture
-        per key.  What the warm-up step advances (the parameters, the moments, the counters and more_state) is put back
-        before the first replay."""
-        g = self.graphs.get(key)
-        if g is None:
-            self._shape(batch[0].shape[0], batch[0].shape[1], True)       # (admission and allocation outside the capture)
-            bufs = [t.clone() for t in batch]
-            state = (self.arena.params, self.arena.exp_avg, self.arena.exp_avg_sq, self.step_t, self.drop_offset) + more_state
-            snap = [t.clone() for t in state]
-            run(bufs)                                                     # warm-up: sizes the GEMM workspaces, sets attributes
-            graph = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graph):
-                out = run(bufs)
-            for dst, src in zip(state, snap):
-                dst.copy_(src)                                            # (undo the warm-up step; a capture runs nothing)
-            g = self.graphs[key] = dict(graph=graph, bufs=bufs, out=out)
-        for dst, src in zip(g["bufs"], batch):
-            dst.copy_(src)
-        g["graph"].replay()
-        return g["out"]
+    eng.pos_embedding_grad(w)

@@ -20,13 +20,11 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
+from .decoder_composed import decoder_drop_sizes, drop_pool
+from .engine_base import DROP_P, EXCLUDE_CLASS_IDX, EngineBase, ParamArena          # noqa: F401  (re-exported)
 
 LIVE_PREFIXES = ("input_embed.", "depth_projection.", "depth_layernorm.", "pos_embedding", "query_embed.",
                  "fuser.blocks.", "fuser.norm.", "transformer.decoder.", "fc_seg.", "fc.", "fc_len.")
-EXCLUDE_CLASS_IDX = 47          # hard-coded at train/train_proposed_depth.py:181,195
-DROP_P = 0.1                    # every nn.Dropout on the path (futr_safuser_tokenfusion.py:26; transformer.py:22)
-
-
 BN_LIVE_PREFIXES = ("fuser.alpha", "fuser.bn_rgb.", "fuser.bn_depth.")    # the BN-blend variant's extra trainable parameters
 VARY_LIVE_PREFIXES = ("fuser.alpha",)                    # the activation-magnitude variant's extra trainable parameter
 PLAIN_LIVE_PREFIXES = ("fuser.modality_token",)          # the plain SA-Fuser's token, added to both tokens of every frame
@@ -35,6 +33,12 @@ PLAIN_LIVE_PREFIXES = ("fuser.modality_token",)          # the plain SA-Fuser's 
 def is_live(name):
     """Parameters that receive a gradient in the reference step; the rest keep grad=None."""
     return name.startswith(LIVE_PREFIXES)
+
+
+def live_rule(extra=()):
+    """ParamArena's rule of a model on this path: is_live plus the prefixes of a variant's own trainable parameters."""
+    extra = tuple(extra)
+    return lambda n: is_live(n) or n.startswith(extra)
 
 
 # Shape admission of the hidden-128 chain launches (csrc/fuser_chain.hip, csrc/decoder_chain.hip), host-only so that the
@@ -134,74 +138,6 @@ def max_clip_len(H, heads, Q, max_pos_len, train):
     return lo
 
 
-class ParamArena:
-    """Flat arenas; live parameters first (AdamW touches only that prefix), depth_projection.weight last among them
-    so that everything else forms one contiguous all-reduce bucket that is ready before the big weight gradient."""
-
-    def __init__(self, named_params, device, extra_live=(), live=None):
-        named = list(named_params)
-        # live: a model's own rule for the parameters that receive a gradient (default: the token-fusion model's + extra_live)
-        self.is_live = live if live is not None else (lambda n: is_live(n) or (bool(extra_live) and n.startswith(tuple(extra_live))))
-        live = [(n, p) for n, p in named if self.is_live(n)]
-        dead = [(n, p) for n, p in named if not self.is_live(n)]
-
-        def key(item):
-            n, p = item
-            if n == "depth_projection.weight":
-                return (3, 0)
-            if n in ("fc.weight", "fc_len.weight"):
-                return (0, 0 if n == "fc.weight" else 1)        # adjacent: [fc.weight ; fc_len.weight] = [K+1, H]
-            if n in ("fc.bias", "fc_len.bias"):
-                return (2, 0 if n == "fc.bias" else 1)          # adjacent: [fc.bias ; fc_len.bias] = [K+1]
-            if n == "pos_embedding":
-                return (2, 9)          # last of the small bucket: only its first S rows ever get a gradient (:190), so a
-                                       # data-parallel step all-reduces the bucket up to row S and skips ~1 MB of zeros
-            return (1, 0) if p.numel() % 4 == 0 else (2, 2)
-        order = sorted(range(len(live)), key=lambda i: (key(live[i]), i))
-        live = [live[i] for i in order]
-        self.offsets, off = {}, 0
-        for n, p in live:
-            if n in ("depth_projection.weight", "pos_embedding"):
-                off = (off + 3) // 4 * 4
-            self.offsets[n] = (off, p.numel(), tuple(p.shape))
-            off += p.numel()
-        self.n_live = (off + 3) // 4 * 4
-        off = self.n_live
-        for n, p in dead:
-            off = (off + 3) // 4 * 4
-            self.offsets[n] = (off, p.numel(), tuple(p.shape))
-            off += p.numel()
-        self.n_total = (off + 3) // 4 * 4
-        big0 = self.offsets["depth_projection.weight"][0] if "depth_projection.weight" in self.offsets else self.n_live
-        self.bucket_small = (0, big0)           # (models without a depth projection: everything is the small bucket)
-        self.bucket_big = (big0, self.n_live)
-        self.params = torch.zeros(self.n_total, dtype=torch.float32, device=device)
-        self.grads = torch.zeros(self.n_live, dtype=torch.float32, device=device)
-        self.exp_avg = torch.zeros(self.n_live, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(self.n_live, dtype=torch.float32, device=device)
-        self.live_names = [n for n, _ in live]
-        with torch.no_grad():
-            for n, p in named:
-                o, k, shp = self.offsets[n]
-                self.params[o:o + k].copy_(p.detach().reshape(-1).to(device=device, dtype=torch.float32))
-                p.data = self.params[o:o + k].view(shp)
-                p.grad = None
-
-    def p(self, name):
-        o, k, shp = self.offsets[name]
-        return self.params[o:o + k].view(shp)
-
-    def g(self, name):
-        o, k, shp = self.offsets[name]
-        return self.grads[o:o + k].view(shp)
-
-    def attach_grads(self, named_params):
-        """Expose the arena gradients as p.grad views (after a fused backward) so that any torch optimiser, gradient
-        clipping or inspection code sees them.  Parameters the reference leaves without a gradient keep grad=None."""
-        for n, p in named_params:
-            p.grad = self.g(n) if self.is_live(n) else None
-
-
 class _Shape:
     """Activation / gradient workspace for one (B, S, mode) shape."""
 
@@ -265,16 +201,15 @@ class _Shape:
             if eng.plain:                                # per-frame modality-token partials (column sum = d modality_token)
                 self.t_tok = f(N, H)
             # dropout keep-masks (one Philox launch fills the whole pool)
-            from .decoder_composed import decoder_drop_sizes, drop_pool          # (that module imports this one)
             self.drop_pool, self.drop = drop_pool({"x0": 2 * N * H, **decoder_drop_sizes(L, B, heads, H, BQ, Q, S)}, dev)
 
 
-class FusionEngine:
+class FusionEngine(EngineBase):
+    _Shape = _Shape
+    fused_loss_flow = True
+    rank_penalty = True
+
     def __init__(self, module, device):
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
-        ops._lib.load()
         self.H, self.Q, self.K = module.hidden_dim, module.n_query, module.n_class
         self.heads, self.L = module.n_head, module.num_decoder_layers
         self.dh = self.H // self.heads
@@ -295,8 +230,7 @@ class FusionEngine:
         self.max_pos_len = module.pos_embedding.shape[1]
         extra = (BN_LIVE_PREFIXES if self.bn else (VARY_LIVE_PREFIXES if self.vary else
                                                    (PLAIN_LIVE_PREFIXES if self.plain else ())))
-        self.arena = ParamArena(list(module.named_parameters()), self.device, extra)
-        self.ws = ops.GemmWorkspace(self.device)
+        self._init_engine(module, device, live_rule(extra))
         self._sel = {}                                  # constant 0/1 selection matrices of _wgrad_with_sums
         self.ws_side = ops.GemmWorkspace(self.device)
         self.side = torch.cuda.Stream(self.device)      # weight-gradient stream: off the backward's critical path
@@ -364,7 +298,6 @@ class FusionEngine:
         # kernel then leaves the reduction of its per-unit partials (loss / counter statistics only the host reads) to
         # one extra workgroup of the AdamW launch -- w.loss / w.counts are valid after adamw(), not after losses()
         self.defer_loss_reduce = False
-        self.loss_acc = None                    # (float64[4], int64[4]) running sums the deferred reduction also feeds
         # the bias / broadcast-parameter / LayerNorm-parameter sums at the end of the backward as problems of the grouped
         # weight-gradient launch (a column sum over the rows of a residue class is a TN product with a constant 0/1
         # selection matrix) instead of a launch of their own
@@ -415,47 +348,15 @@ class FusionEngine:
         self.er_stream = torch.cuda.Stream(self.device)
         self.ws_er = ops.GemmWorkspace(self.device)
         self._er_pending = False
-        self.shapes = {}
         self.train_mask = None            # cached train-mode selection (data independent)
         # the plain fuser's exchange masks: all zero (the chain backward's exchange adjoint is then the identity)
         self.plain_mask = torch.zeros(2, self.H, dtype=torch.float32, device=self.device) if self.plain else None
-        self.drop_seed = 0x5EED
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._lr_host = None
-        self.dur_den = None               # device scalar set by the data-parallel wrapper
-        self.score_allreduce = None       # callable(sums fp64 [2,H]) -> global row count, set by the DP wrapper
-        self.bn_sync = None               # parallel.SyncBatchNorm, set by the DP wrapper for the BN-blend variant
-        self.grad_hook = None             # callable(stage) set by the DP wrapper: "small_ready" / "big_ready"
-        self.tp = None                    # parallel.PixelShardedDepth: depth_projection tensor-parallel over pixels
         self._fw = None
-        self.last = None
-        self.rank_stream = None           # [(workspace attribute, rankstream.StreamingRank)]: fed by every forward while set
         self._adam = None
-        self._drop_ready = None           # workspace whose dropout pool already holds the masks of the next forward
-        # high-water mark of the pos_embedding gradient rows a backward has written: a step only writes its first S rows
-        # (:190), so every backward clears rows [S, pos_grad_rows) left by a longer earlier batch (monotone, so a step
-        # captured in a hipGraph clears what any step before its capture could have written; train() re-captures when it
-        # grows)
-        self.pos_grad_rows = 0
-        a = self.arena
-        K, H = self.K, self.H
-        o_w = a.offsets["fc.weight"][0]
-        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        o_b = a.offsets["fc.bias"][0]
-        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K
-        self.b_head = a.params[o_b:o_b + K + 1]
-        self.gb_head = a.grads[o_b:o_b + K + 1]
 
     # ------------------------------------------------------------------------------------------------------
-    def _shape(self, B, S, train):
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            check_clip_shape(S, self.H, self.heads, self.Q, self.max_pos_len, train)    # (before anything is enqueued)
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
+    def _admit(self, B, S, train):
+        check_clip_shape(S, self.H, self.heads, self.Q, self.max_pos_len, train)
 
     def _train_masks(self, B, S):
         """train mode: score = |d(mean)/dx| averaged over (B,T) = the constant 1/(B*T*C) for every channel
@@ -1108,10 +1009,6 @@ class FusionEngine:
             tab.arr[22] = key_labels.data_ptr() if key_labels is not None else None
             ops.decoder_layer_fwd(tab, B, S, Q, H, heads, self.pad_idx, dsc, K + 1)
 
-    @staticmethod
-    def _dm2(m, rows, cols):
-        return None if m is None else m.view(rows, cols)
-
     # ------------------------------------------------------------------------------------------------------
     def losses(self, past_label, target, target_dur, with_grad=True, val_mode=False, tick=False):
         """The 3 losses + counters of train_proposed_depth.py:171-213 in one launch; fills d_seg / d_actdur.
@@ -1719,14 +1616,6 @@ class FusionEngine:
             ops.rowmod_sum(gl["sain"], Q, g_qe, accumulate=True)
 
     # ------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr):
-        """True when it enqueued a new value (on the current stream)."""
-        if self._lr_host != float(lr):          # lr lives in device memory so a captured graph sees scheduler updates
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-            return True
-        return False
-
     def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
               skip_depth=False, prefill_dropout=False, before_flat=None):
         """One fused launch over the live prefix of the arena (main_darai.py:135; train_proposed_depth.py:215).
@@ -1738,7 +1627,6 @@ class FusionEngine:
         (valid while the next forward uses the same shape and the dropout offset is not advanced again)."""
         a = self.arena
         filled = self.set_lr(lr)
-        kw = dict(beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
         n0 = 0
         if self._tail_pending and ticked and self.tp is None and not skip_depth and before_flat is None:
             # the branch that produced the small bucket's gradients goes on to update it; this stream keeps the one weight
@@ -1748,34 +1636,30 @@ class FusionEngine:
                                                 # (train_step and train() set lr before the step: no join there)
                 self.side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self.side):
-                ops.adamw_flat(a.params[:n0], a.grads[:n0], a.exp_avg[:n0], a.exp_avg_sq[:n0], self.lr_t, self.step_t, **kw)
+                self._adamw_flat(0, n0, weight_decay, betas, eps, grad_scale)
         else:
             self._join_tail()
         if not ticked:
-            ops.tick(self.step_t, self.drop_offset if tick_dropout else None)
+            ops.tick(self.step_t, self._tick_counter(tick_dropout))
         n = a.n_live if (self.tp is None and not skip_depth) else a.bucket_small[1]
         st = self.last
         depth_cols_first = before_flat is not None and self.tp is not None and not skip_depth
         if depth_cols_first:
-            t = self.tp
-            ops.adamw_2d(t.w, t.g, t.m, t.v, self.lr_t, self.step_t, beta1=betas[0], beta2=betas[1], eps=eps,
-                         weight_decay=weight_decay, grad_scale=grad_scale)
+            self._adamw_depth_cols(weight_decay, betas, eps, grad_scale)
         if before_flat is not None:
             before_flat()
-        pending, self._loss_pending = getattr(self, "_loss_pending", None), None
-        if prefill_dropout and st is not None and st["drop"] and (ticked or tick_dropout):
-            ops.adamw_flat_dropout(a.params[n0:n], a.grads[n0:n], a.exp_avg[n0:n], a.exp_avg_sq[n0:n], self.lr_t, self.step_t,
-                                   st["w"].drop_pool, DROP_P, self.drop_seed, self.drop_offset, loss_fin=pending, **kw)
-            self._drop_ready = st["w"]
-            pending = None
-        else:
-            ops.adamw_flat(a.params[n0:n], a.grads[n0:n], a.exp_avg[n0:n], a.exp_avg_sq[n0:n], self.lr_t, self.step_t,
-                           loss_fin=pending, **kw)
+        pending, self._loss_pending = self._loss_pending, None
+        prefill = prefill_dropout and st is not None and st["drop"] and (ticked or tick_dropout)
+        self._adamw_flat(n0, n, weight_decay, betas, eps, grad_scale, loss_fin=pending, prefill=st["w"] if prefill else None)
         self._join_tail()
         if self.tp is not None and not skip_depth and not depth_cols_first:
-            t = self.tp                             # depth_projection.weight: only this rank's pixel columns are live
-            ops.adamw_2d(t.w, t.g, t.m, t.v, self.lr_t, self.step_t, beta1=betas[0], beta2=betas[1], eps=eps,
-                         weight_decay=weight_decay, grad_scale=grad_scale)
+            self._adamw_depth_cols(weight_decay, betas, eps, grad_scale)
+
+    def _adamw_depth_cols(self, weight_decay, betas, eps, grad_scale):
+        """depth_projection.weight under the pixel-sharded projection: only this rank's pixel columns are live"""
+        t = self.tp
+        ops.adamw_2d(t.w, t.g, t.m, t.v, self.lr_t, self.step_t, beta1=betas[0], beta2=betas[1], eps=eps,
+                     weight_decay=weight_decay, grad_scale=grad_scale)
 
     def train_step(self, feats, depth, past_label, target_dur, target, lr, weight_decay, training=True):
         """forward + losses + backward + AdamW, all enqueued, no host sync.  Returns (loss[4], counts[4]) on device."""

@@ -19,7 +19,8 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .engine import DROP_P, EXCLUDE_CLASS_IDX, SEAM_MAX_H, ParamArena, check_hidden
+from .engine import SEAM_MAX_H, check_hidden
+from .engine_base import DROP_P, EXCLUDE_CLASS_IDX, EngineBase
 
 AFFT_LIVE_PREFIXES = ("input_embed.", "depth_projection.", "depth_layernorm.", "fuser.blocks.0.", "fuser.norm.",
                       "fuser.modality_token", "fc.", "fc_len.")
@@ -111,52 +112,28 @@ class _Shape:
             self.drop = {"x0": self.drop_pool[:2 * N * H]}               # embd_drop: the model's only dropout on the path
 
 
-class AfftEngine:
+class AfftEngine(EngineBase):
+    _Shape = _Shape
+    fused_loss_flow = True
+    plain = True                                # (what rankstream and the tools ask a fuser engine)
+
     def __init__(self, module, device):
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
         check_afft_args(seg=bool(getattr(module.args, "seg", False)))          # (before anything is allocated)
         self.H, self.Q, self.K, self.heads = module.hidden_dim, module.n_query, module.n_class, module.n_head
         check_afft_shape(1, 1, self.H, self.heads, self.Q, self.K)
-        ops._lib.load()
+        self._init_engine(module, device, is_live)
         self.pad_idx = module.src_pad_idx
         self.P, self.D = module.depth_projection.in_features, module.input_embed.in_features
-        self.plain = True                       # (what rankstream and the tools ask a fuser engine)
-        self.arena = ParamArena(list(module.named_parameters()), self.device, live=is_live)
-        self.ws = ops.GemmWorkspace(self.device)
         self.ws_side = ops.GemmWorkspace(self.device)
         self.use_gemm_ln = True                 # hidden = 128: Linear + residual + LayerNorm sites as one launch (gemm_ln.hip)
         self.pair_embeddings = True             # both input projections in one launch (ops.gemm_bf3_nt_pair) where it applies
         self.depth_prec = 1                     # the two depth-projection GEMMs on the bf16 matrix cores (exact 3-way split)
         # the training step's tail as ONE launch (csrc/afft.hip) where chain_pays(); None: by shape, True / False: forced
         self.use_head_chain = None
-        # forward -> losses -> backward flows set this: forward() then leaves pool and heads to the chain launch in losses();
-        # its outputs are valid only after losses()
-        self.defer_tail = False
         # fused flows (losses(tick=True) ... adamw(ticked=True)): the loss partials are reduced by one extra workgroup of the
         # AdamW launch -- w.loss / w.counts are valid after adamw(), not after losses()
         self.defer_loss_reduce = False
-        self.loss_acc = None
-        self._loss_pending = None
         self.dropout_enabled = bool(getattr(module, "r3d_dropout_enabled", True))
-        self.shapes = {}
-        self.drop_seed = 0x5EED
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._lr_host = None
-        self._drop_ready = None
-        self.rank_stream = None           # [(workspace attribute, rankstream.StreamingRank)]: fed by every forward while set
-        self.last = None
-        a, K, H = self.arena, self.K, self.H
-        o_w = a.offsets["fc.weight"][0]
-        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        o_b = a.offsets["fc.bias"][0]
-        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K and o_w % 4 == 0
-        self.b_head = a.params[o_b:o_b + K + 1]
-        self.gb_head = a.grads[o_b:o_b + K + 1]
 
     # ---- what the engine does not run: refused where the caller asks for it, before any launch ---------------------------
     @property
@@ -177,12 +154,8 @@ class AfftEngine:
     tp = property(lambda self: None, _refused_parallel)
 
     # ------------------------------------------------------------------------------------------------------
-    def _shape(self, B, S, train):
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            check_afft_shape(B, S, self.H, self.heads, self.Q, self.K)          # (before anything is enqueued)
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
+    def _admit(self, B, S, train):
+        check_afft_shape(B, S, self.H, self.heads, self.Q, self.K)
 
     def _gln(self, rows, K):
         return self.use_gemm_ln and ops.gemm_ln_supported(rows, K, self.H)
@@ -334,9 +307,6 @@ class AfftEngine:
         self.backward_main(d_actdur=d_actdur)
         self.backward_depth_wgrad()
 
-    def depth_adamw_fusable(self):
-        return False
-
     def backward_main(self, d_seg=None, d_actdur=None):
         st = self.last
         w, a, H, Q, ws = st["w"], self.arena, self.H, self.Q, self.ws
@@ -379,33 +349,20 @@ class AfftEngine:
                  prec=self.depth_prec)
 
     # ------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr):
-        if self._lr_host != float(lr):          # lr lives in device memory so a captured graph sees scheduler updates
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-            return True
-        return False
-
     def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
               skip_depth=False, prefill_dropout=False, before_flat=None):
         """One fused launch over the live prefix of the arena; the dead parameters are outside it.  ticked: losses(tick=True)
         already advanced the counters.  prefill_dropout: the launch also fills the workspace's dropout pool with the NEXT
         step's masks.  A loss reduction left pending by losses() rides as one more workgroup."""
         assert not skip_depth and before_flat is None
-        a = self.arena
         self.set_lr(lr)
-        kw = dict(beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
         if not ticked:
-            ops.tick(self.step_t, self.drop_offset if tick_dropout else None)
-        n, st = a.n_live, self.last
+            ops.tick(self.step_t, self._tick_counter(tick_dropout))
+        st = self.last
         pending, self._loss_pending = self._loss_pending, None
-        if prefill_dropout and st is not None and st["drop"] and (ticked or tick_dropout):
-            ops.adamw_flat_dropout(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t,
-                                   st["w"].drop_pool, DROP_P, self.drop_seed, self.drop_offset, loss_fin=pending, **kw)
-            self._drop_ready = st["w"]
-        else:
-            ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t,
-                           loss_fin=pending, **kw)
+        prefill = prefill_dropout and st is not None and st["drop"] and (ticked or tick_dropout)
+        self._adamw_flat(0, self.arena.n_live, weight_decay, betas, eps, grad_scale, loss_fin=pending,
+                         prefill=st["w"] if prefill else None)
 
     def train_step(self, feats, depth, past_label, target_dur, target, lr, weight_decay, training=True):
         """forward + losses + backward + AdamW, all enqueued, no host sync.  Returns (loss[4], counts[4]) on device."""

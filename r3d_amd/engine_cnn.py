@@ -30,7 +30,7 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .engine import ParamArena
+from .engine_base import EngineBase
 
 EXCLUDE_CLASS_IDX = 120         # NTU's UNDEFINED class, hard-coded at train/train_unimodal.py:102,198,212
 POOL_ROWS = 8                   # F.adaptive_avg_pool1d(tgt, 8) (model/cnn.py:94)
@@ -112,46 +112,24 @@ class _Shape:
             self.d_extra = self._f(*self.d_x0.shape)
 
 
-class CnnEngine:
+class CnnEngine(EngineBase):
+    _Shape = _Shape
+    defer_tail = True                       # a training forward() leaves everything behind x to losses() on the chain route
+
     def __init__(self, module, device):
         self.H, self.Q, self.K = module.hidden_dim, POOL_ROWS, module.n_class
         self.D = module.input_embed.in_features
         check_cnn_shape(self.H, module.n_query, self.K, input_dim=self.D)          # (before anything is enqueued)
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
-        ops._lib.load()
+        self._init_engine(module, device, is_live)
         self.Kseg = module.fc_seg.out_features
         self.pad_idx = module.src_pad_idx
-        self.arena = ParamArena(list(module.named_parameters()), self.device, live=is_live)
-        self.ws = ops.GemmWorkspace(self.device)
         self._erank_weight = 0.0
         self.supcon_weight = 0.0            # --supcon_weight: total loss += weight * SupConLoss over the 'supcon' rows (x)
         self.supcon_temperature = 0.07      # --temperature
         # the step's two branches as two launches (csrc/afft.hip, csrc/cnn.hip) where both admit the shape and chain_pays();
         # None: by shape, True: wherever admitted, False: the composed launches
         self.use_seg_chain = None
-        self.defer_tail = True              # a training forward() leaves everything behind x to losses() on the chain route
         self.ride_loss_reduce = True        # losses(tick=True) on the chain: the AdamW launch reduces the loss partials
-        self.shapes = {}
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)     # (no dropout: kept for the surface)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._lr_host = None
-        self.dur_den = None
-        self.grad_hook = None
-        self.tp = None
-        self._drop_ready = None
-        self._loss_pending = None
-        self.last = None
-        a, K, H = self.arena, self.K, self.H
-        o_w = a.offsets["fc.weight"][0]
-        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        o_b = a.offsets["fc.bias"][0]
-        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K and o_w % 4 == 0
-        self.b_head = a.params[o_b:o_b + K + 1]
-        self.gb_head = a.grads[o_b:o_b + K + 1]
 
     @property
     def erank_weight(self):
@@ -161,12 +139,8 @@ class CnnEngine:
     def erank_weight(self, v):
         check_cnn_shape(self.H, POOL_ROWS, self.K, erank_weight=float(v))
 
-    def _shape(self, B, S, train):
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            check_cnn_shape(self.H, POOL_ROWS, self.K, B=B, S=S, input_dim=self.D)     # (before anything is enqueued)
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
+    def _admit(self, B, S, train):
+        check_cnn_shape(self.H, POOL_ROWS, self.K, B=B, S=S, input_dim=self.D)
 
     def chain_admitted(self):
         return ops.cnn_seg_supported(self.H, self.Kseg) and ops.afft_head_supported(self.H, POOL_ROWS, self.K + 1)
@@ -303,24 +277,16 @@ class CnnEngine:
         wgrad(w.d_pre, st["x_rgb"], a.g("input_embed.weight"), a.g("input_embed.bias"))
 
     # ------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr):
-        if self._lr_host != float(lr):
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-
     def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
               skip_depth=False, prefill_dropout=False, before_flat=None):
         """One fused launch over the live prefix of the arena (main_nturgbd.py:140; train_unimodal.py:230).  A loss
         reduction left pending by a chain losses(tick=True) rides as one more workgroup."""
-        a = self.arena
         self.set_lr(lr)
         if not ticked:
-            ops.tick(self.step_t, None)
-        n = a.n_live
+            ops.tick(self.step_t, None)     # (no dropout: nothing else to advance)
         pending, self._loss_pending = self._loss_pending, None
         job, sc_w = pending if pending is not None else (None, None)
-        ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t, beta1=betas[0],
-                       beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, loss_fin=job)
+        self._adamw_flat(0, self.arena.n_live, weight_decay, betas, eps, grad_scale, loss_fin=job)
         if sc_w is not None:
             sc_w.loss[3:4].add_(sc_w.sc_loss, alpha=self.supcon_weight)
 

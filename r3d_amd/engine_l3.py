@@ -21,8 +21,9 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .decoder_composed import ComposedEngine, DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
-from .engine import ParamArena, DROP_P, check_hidden, max_clip_len
+from .decoder_composed import DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
+from .engine import check_hidden, max_clip_len
+from .engine_base import DROP_P, EngineBase
 
 LIVE_PREFIXES = ("input_embed.", "l3_attention.", "transformer.decoder.", "pos_embedding", "fc_seg.", "fc.", "fc_len.",
                  "fc_l3.")
@@ -31,6 +32,10 @@ VAL_L3_PAD = 48                   # validate() calls it with pad 48 (:163)
 MAX_CLIPS = 64                    # the cross-clip attention holds the B x B scores of a (frame, head) in LDS
 MAX_QUERY_NUM = 256               # the cluster kernel's width
 MAX_SEG_CLASSES = 1023
+
+
+def is_live(name):
+    return name.startswith(LIVE_PREFIXES)
 
 
 def check_l3_shape(H, heads, Q, query_num, n_class):
@@ -91,37 +96,28 @@ class _Shape:
             self.d_pool, self.d_l3, self.d_xo, self.d_xqkv, self.d_rgb_pre = f(N, H), f(N, H), f(N, H), f(N, 3 * H), f(N, H)
 
 
-class L3Engine(ComposedEngine):
+class L3Engine(EngineBase):
+    _Shape = _Shape
+
     def __init__(self, module, device):
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
-        ops._lib.load()
         self.H, self.Q, self.K = module.hidden_dim, module.n_query, module.n_class
         self.heads, self.L = module.n_head, module.num_decoder_layers
         self.C = module.fc_l3.out_features                        # query_num
         self.Kseg = module.fc_seg.out_features                    # n_class (not n_class - 1)
         check_l3_shape(self.H, self.heads, self.Q, self.C, self.Kseg)
+        self._init_engine(module, device, is_live)
         self.dh = self.H // self.heads
         self.pad_idx = module.src_pad_idx
         self.D = module.input_embed.in_features
-        self.arena = ParamArena(list(module.named_parameters()), self.device, live=lambda n: n.startswith(LIVE_PREFIXES))
         self.pe = module.pos_enc.pos_table[0]
         self.pe_l3 = module.positional_embedding_l3.to(self.device).contiguous()
         self.max_pos_len = min(module.pos_embedding.shape[1], self.pe.shape[0], self.pe_l3.shape[0])
-        self.ws = ops.GemmWorkspace(self.device)
         self.dropout_enabled = bool(getattr(module, "r3d_dropout_enabled", True))
-        self.erank_weight = 0.0
         self.wf_t = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._wf_host = None
-        self._init_step_state()
 
-    def _shape(self, B, S, train):
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            check_l3_batch(B, S, self.H, self.heads, self.Q, self.max_pos_len, train)      # (before anything is enqueued)
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
+    def _admit(self, B, S, train):
+        check_l3_batch(B, S, self.H, self.heads, self.Q, self.max_pos_len, train)
 
     # ------------------------------------------------------------------------------------------------------
     def forward(self, feats, labels, mode="train", training=False, need_grad=True):
@@ -226,12 +222,8 @@ class L3Engine(ComposedEngine):
         wgrad(w.d_rgb_pre, st["x"], a.g("input_embed.weight"), a.g("input_embed.bias"))
 
     # ------------------------------------------------------------------------------------------------------
-    def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, ticked=False):
-        """One fused launch over the live prefix of the arena."""
-        self.set_lr(lr)
-        if not ticked:
-            ops.tick(self.step_t, self.drop_offset if (self.last and self.last["drop"]) else None)
-        self._adamw_flat(weight_decay, betas, eps)
+    def _tick_counter(self, tick_dropout):
+        return self.drop_offset if (self.last and self.last["drop"]) else None      # (whatever the caller says)
 
     def train_step(self, feats, past_label, target_dur, target, query_label, lr, weight_decay, wf, training=True,
                    betas=(0.9, 0.999), eps=1e-8, acc=None):

@@ -33,11 +33,12 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .decoder_composed import ComposedEngine, DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
-from .engine import (DROP_P, EXCLUDE_CLASS_IDX, ERANK_ROUTES, SEAM_MAX_H, ParamArena, check_hidden, check_erank_shape,
-                     max_clip_len)
+from .decoder_composed import DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
+from .engine import ERANK_ROUTES, SEAM_MAX_H, check_hidden, check_erank_shape, live_rule, max_clip_len
+from .engine_base import DROP_P, EXCLUDE_CLASS_IDX, EngineBase
 
 M3_LIVE_EXTRA = ("gaze_projection.", "gaze_layernorm.")
+is_live = live_rule(M3_LIVE_EXTRA)
 M3_MAX_GAZE = ops.FUSE3_MAX_GAZE
 M3_MAX_CLASSES = 1023           # the loss kernels' class limit
 M3_MAX_HEAD_WIDTH = 128         # r3d_attn3_* (two channels per lane) and the decoder attention cores
@@ -143,38 +144,31 @@ class _Shape:
             self.lnp_seam = dict(n1=f(2 * N * H), dep=f(2 * N * H), gz=f(2 * N * H))     # one (dgamma, dbeta) pair per frame
 
 
-class M3Engine(ComposedEngine):
+class M3Engine(EngineBase):
+    _Shape = _Shape
+    rank_penalty = True
+
     def __init__(self, module, device):
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
         args = module.args
         check_m3_args(seg=bool(getattr(args, "seg", True)), anticipate=bool(getattr(args, "anticipate", True)),
                       input_type=getattr(args, "input_type", "i3d_transcript"))          # (before anything is allocated)
         self.H, self.Q, self.K = module.hidden_dim, module.n_query, module.n_class
         self.heads, self.L, self.G = module.n_head, module.num_decoder_layers, module.gaze_dim
         check_m3_shape(self.H, self.heads, self.Q, self.K, self.G)
-        ops._lib.load()
+        self._init_engine(module, device, is_live)
         self.dh = self.H // self.heads
         self.pad_idx = module.src_pad_idx
         self.P, self.D = module.depth_projection.in_features, module.input_embed.in_features
         self.max_pos_len = module.pos_embedding.shape[1]
-        self.arena = ParamArena(list(module.named_parameters()), self.device, extra_live=M3_LIVE_EXTRA)
-        self.ws = ops.GemmWorkspace(self.device)
         self.ws_side = ops.GemmWorkspace(self.device)
         self.use_seam = None                    # None: seam_pays(N, H); True / False: forced
         self.pair_embeddings = True             # both input projections in one launch (ops.gemm_bf3_nt_pair) where it applies
         self.depth_prec = 1                     # the two depth-projection GEMMs on the bf16 matrix cores (exact 3-way split)
         self.dropout_enabled = bool(getattr(module, "r3d_dropout_enabled", True))
         self._erank_weight, self._erank_route = 0.0, "jacobi"
-        self.erank_fold = None
         self.erank_max_sweeps = 30
-        self._drop_ready = None                 # (the loop clears it; this engine never prefills a dropout pool)
-        self.grad_hook = self.score_allreduce = self.dur_den = self.tp = None     # (one GPU: see refuse_data_parallel)
-        self.rank_stream = None
         self.train_mask = None
         self.last_idx = None
-        self._init_step_state()
 
     def refuse_data_parallel(self):
         """parallel.DataParallelStep asks this of an engine before it hooks into it: this one runs on one GPU"""
@@ -200,11 +194,9 @@ class M3Engine(ComposedEngine):
 
     # ------------------------------------------------------------------------------------------------------
     def _shape(self, B, S, train):
+        # (admitted on every call, not only before the first allocation: the penalty's weight and route change between steps)
         check_m3_batch(B, S, self.H, self.heads, self.Q, self.max_pos_len, train, self._erank_weight, self._erank_route)
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
+        return super()._shape(B, S, train)
 
     def _seam(self, w):
         return seam_pays(w.N, self.H) if self.use_seam is None else bool(self.use_seam)
@@ -391,9 +383,6 @@ class M3Engine(ComposedEngine):
         self.backward_main(d_seg, d_actdur)
         self.backward_depth_wgrad()
 
-    def depth_adamw_fusable(self):
-        return False
-
     def backward_main(self, d_seg=None, d_actdur=None):
         """Everything of the backward except depth_projection.weight."""
         st = self.last
@@ -470,17 +459,6 @@ class M3Engine(ComposedEngine):
                  prec=self.depth_prec)
 
     # ------------------------------------------------------------------------------------------------------
-    def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
-              skip_depth=False, prefill_dropout=False, before_flat=None):
-        """One fused launch over the live prefix of the arena; the dead parameters are outside it.  ticked: losses(tick=True)
-        already advanced the counters.  (prefill_dropout is accepted for the loop's calling convention; every forward of this
-        engine generates its own masks.)"""
-        assert not skip_depth and before_flat is None
-        self.set_lr(lr)
-        if not ticked:
-            ops.tick(self.step_t, self.drop_offset if tick_dropout else None)
-        self._adamw_flat(weight_decay, betas, eps, grad_scale)
-
     def train_step(self, feats, depth, past_label, target_dur, target, lr, weight_decay, training=True, gaze=None,
                    betas=(0.9, 0.999), eps=1e-8):
         """forward + losses + backward + AdamW, all enqueued, no host sync.  Returns (loss[4], counts[4]) on device."""

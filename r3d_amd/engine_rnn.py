@@ -16,7 +16,7 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .engine import ParamArena
+from .engine_base import EngineBase
 
 EXCLUDE_CLASS_IDX = 120         # NTU's UNDEFINED class, hard-coded at train/train_unimodal.py:102,198,212
 POOL_ROWS = 8                   # F.adaptive_avg_pool1d(tgt, 8) (model/rnn.py:97)
@@ -25,6 +25,10 @@ RNN_MIN_H, RNN_MAX_H = 8, 256   # the recurrence kernels' range (csrc/lstm.hip: 
 SUPCON_BASE_T = 0.07            # SupConLoss's default base_temperature (loss/spc.py:69); the entry scripts pass temperature only
 
 RNN_LIVE_PREFIXES = ("input_embed.", "rnn.", "rnn_fc.", "fc_seg.", "fc.", "fc_len.")
+
+
+def is_live(name):
+    return name.startswith(RNN_LIVE_PREFIXES)
 
 
 def check_rnn_shape(H, n_query=POOL_ROWS, erank_weight=0.0):
@@ -85,42 +89,19 @@ class _Shape:
             self.sc_ws, self.sc_loss = f(ops.supcon_ws_floats(N)), torch.zeros(1, dtype=torch.float32, device=dev)
 
 
-class RnnEngine:
+class RnnEngine(EngineBase):
+    _Shape = _Shape
+
     def __init__(self, module, device):
         check_rnn_shape(module.hidden_dim, module.n_query)          # (before anything is enqueued)
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
-        ops._lib.load()
         self.H, self.Q, self.K = module.hidden_dim, POOL_ROWS, module.n_class
+        self._init_engine(module, device, is_live, _arena_order(list(module.named_parameters())))
         self.Kseg = module.fc_seg.out_features
         self.D = module.input_embed.in_features
         self.pad_idx = module.src_pad_idx
-        self.arena = ParamArena(_arena_order(list(module.named_parameters())), self.device,
-                                live=lambda n: n.startswith(RNN_LIVE_PREFIXES))
-        self.ws = ops.GemmWorkspace(self.device)
-        self.erank_weight = 0.0
         self.supcon_weight = 0.0            # --supcon_weight: total loss += weight * SupConLoss over the 'supcon' rows
         self.supcon_temperature = 0.07      # --temperature
-        self.defer_tail = False
-        self.shapes = {}
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)     # (no dropout: kept for the surface)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._lr_host = None
-        self.dur_den = None
-        self.grad_hook = None
-        self.tp = None
-        self._drop_ready = None
-        self.last = None
-        a, K, H = self.arena, self.K, self.H
-        o_w = a.offsets["fc.weight"][0]
-        self.w_head = a.params[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        self.gw_head = a.grads[o_w:o_w + (K + 1) * H].view(K + 1, H)
-        o_b = a.offsets["fc.bias"][0]
-        assert a.offsets["fc_len.weight"][0] == o_w + K * H and a.offsets["fc_len.bias"][0] == o_b + K
-        self.b_head = a.params[o_b:o_b + K + 1]
-        self.gb_head = a.grads[o_b:o_b + K + 1]
+        a, H = self.arena, self.H
         # per layer: [W_ih fwd; W_ih rev] as one [4H, H] operand, [b_ih fwd; b_ih rev] as one [4H] bias
         self.w_ih, self.gw_ih, self.b_ih, self.gb_ih = [], [], [], []
         for l in range(2):
@@ -131,12 +112,6 @@ class RnnEngine:
             self.gw_ih.append(a.grads[ow:ow + 4 * H * H].view(4 * H, H))
             self.b_ih.append(a.params[ob:ob + 4 * H])
             self.gb_ih.append(a.grads[ob:ob + 4 * H])
-
-    def _shape(self, B, S, train):
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
 
     def _whh(self, l, grad=False):
         f = self.arena.g if grad else self.arena.p
@@ -239,21 +214,8 @@ class RnnEngine:
         wgrad(w.d_pre, st["x_rgb"], a.g("input_embed.weight"), a.g("input_embed.bias"))
 
     # ------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr):
-        if self._lr_host != float(lr):
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-
-    def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
-              skip_depth=False, prefill_dropout=False, before_flat=None):
-        """One fused launch over the live prefix of the arena (main_nturgbd.py:140; train_unimodal.py:230)."""
-        a = self.arena
-        self.set_lr(lr)
-        if not ticked:
-            ops.tick(self.step_t, None)
-        n = a.n_live
-        ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t, beta1=betas[0],
-                       beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+    def _tick_counter(self, tick_dropout):
+        return None                         # (no dropout: nothing beside the step counter to advance)
 
     def train_step(self, feats, depth, past_label, target_dur, target, lr, weight_decay, training=True):
         """forward + losses + backward + AdamW, all enqueued, no host sync.  Returns (loss[4], counts[4]) on device.

@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .engine import ParamArena
+from .engine_base import EngineBase
 
 TCN_IN = 2048
 TCN_CHANNELS = (256, 512, 512, 256)
@@ -42,6 +42,10 @@ def check_tcn_shape(B, S, num_classes, anticipated_frames=8):
     if anticipated_frames * num_classes > TCN_MAX_HEAD:
         raise ValueError(f"anticipated_frames * num_classes = {anticipated_frames * num_classes}: the regression head takes "
                          f"at most {TCN_MAX_HEAD} outputs")
+
+
+def is_live(name):
+    return True                         # (every parameter receives a gradient)
 
 
 class _Level:
@@ -87,26 +91,14 @@ class _Shape:
                                            for ci, co in ((L.c_in, L.c_out), (L.c_out, L.c_out)))))
 
 
-class TcnEngine:
+class TcnEngine(EngineBase):
+    _Shape = _Shape
+
     def __init__(self, module, device):
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
         self.K, self.Q = module.num_classes, module.anticipated_frames
         check_tcn_shape(1, 1, self.K, self.Q)                        # (before anything is enqueued)
-        ops._lib.load()
         self.levels = [_Level(i, TCN_IN if i == 0 else TCN_CHANNELS[i - 1], c) for i, c in enumerate(TCN_CHANNELS)]
-        self.arena = ParamArena(list(module.named_parameters()), self.device, live=lambda n: True)
-        self.ws = ops.GemmWorkspace(self.device)
-        self.shapes = {}
-        self.erank_weight = 0.0
-        self.drop_seed = 0x5EED
-        self.drop_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._lr_host = None
-        self._drop_ready = None
-        self.last = None
+        self._init_engine(module, device, is_live)
         # per convolution: s = g / |v|, 1 / |v| and the rank-one coefficient <G_o, v_o> / |v_o|^2
         tot = sum(2 * L.c_out for L in self.levels)
         self.scales = torch.zeros(3, tot, dtype=torch.float32, device=self.device)
@@ -119,12 +111,6 @@ class TcnEngine:
     def _sc(self, name, k):
         o, n = self.slot[name]
         return self.scales[k, o:o + n]
-
-    def _shape(self, B, S, train):
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
 
     def workspace_shapes(self, B, S, train=True):
         """(name, shape, dtype) of every buffer a step of (B, S) uses besides the parameter arenas and the per-channel
@@ -237,20 +223,8 @@ class TcnEngine:
             g = g_prev
 
     # ------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr):
-        if self._lr_host != float(lr):
-            self.lr_t.fill_(float(lr))
-            self._lr_host = float(lr)
-
-    def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, ticked=False, **_):
-        """One fused launch over the whole arena (every parameter is live)."""
-        a = self.arena
-        self.set_lr(lr)
-        if not ticked:
-            ops.tick(self.step_t, None)
-        n = a.n_live
-        ops.adamw_flat(a.params[:n], a.grads[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.lr_t, self.step_t, beta1=betas[0],
-                       beta2=betas[1], eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+    def _tick_counter(self, tick_dropout):
+        return None                         # (every dropout forward moves the offset itself: see forward())
 
     def train_step(self, feats, target, pad_idx, lr, weight_decay, training=True, betas=(0.9, 0.999), eps=1e-8):
         """forward + loss + backward + AdamW, all enqueued, no host sync.  Returns (loss[4], counts[4]) on device."""

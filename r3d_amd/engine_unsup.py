@@ -17,8 +17,9 @@ import torch
 
 from . import ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
-from .decoder_composed import ComposedEngine, DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
-from .engine import ParamArena, DROP_P, EXCLUDE_CLASS_IDX, check_hidden
+from .decoder_composed import DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
+from .engine import check_hidden
+from .engine_base import DROP_P, EXCLUDE_CLASS_IDX, EngineBase
 
 
 # Shape admission (as engine.py's): every clip brings S queries, so both decoder attentions run Lq = Lk = S and the core's
@@ -79,12 +80,10 @@ LIVE_PREFIXES = ("input_embed.", "depth_projection.", "depth_layernorm.", "pos_e
                  "fc_seg.", "fc.", "fc_len.", "query_embed.")     # (query_embed: the label-query variant, model/futr_proposed.py)
 
 
-class _Arena(ParamArena):
-    def __init__(self, named_params, device):
-        # ParamArena's rule set is the token-fusion model's; this model has no query_embed / fuser, so the shared prefixes
-        # select exactly the parameters that receive a gradient here (checked against the reference fixture's live set)
-        super().__init__(named_params, device)
-        self.is_live = lambda n: n.startswith(LIVE_PREFIXES)
+def is_live(name):
+    """This model has no fuser, so these prefixes select exactly the parameters that receive a gradient (checked against
+    the reference fixture's live set)."""
+    return name.startswith(LIVE_PREFIXES)
 
 
 class _Shape:
@@ -111,16 +110,15 @@ class _Shape:
             self.d_rgb_pre, self.d_dep, self.d_dep_pre = f(N, H), f(N, H), f(N, H)
 
 
-class UnsupDepthEngine(ComposedEngine):
+class UnsupDepthEngine(EngineBase):
+    _Shape = _Shape
+
     def __init__(self, module, device):
-        self.module = module
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "the HIP engine needs an MI355X device (there is no CPU path)"
-        ops._lib.load()
         self.H, self.Q, self.K = module.hidden_dim, module.n_query, module.n_class
         self.heads, self.L = module.n_head, module.num_decoder_layers
         self.long_clips = bool(getattr(module, "r3d_long_clips", False))       # (opts --long_clips: the tiled attention route)
         check_query_engine_shape(self.H, self.heads, self.long_clips)
+        self._init_engine(module, device, is_live)
         self.dh = self.H // self.heads
         self.pad_idx = module.src_pad_idx
         # label_query: model/futr_proposed.py -- the decoder query is nn.Embedding(label indices) + a sinusoidal table
@@ -129,27 +127,14 @@ class UnsupDepthEngine(ComposedEngine):
         self.D = module.input_embed.in_features
         self.P = None if self.label_query else module.depth_projection.in_features
         self.Kseg = module.fc_seg.out_features
-        self.arena = _Arena(list(module.named_parameters()), self.device)
         self.pe = module.pos_enc.pos_table[0]                     # [3000, H] sinusoid buffer (position.py:19-27)
         self.pe_depth = None if self.label_query else module.pos_enc_depth.pos_table[0]
         self.pe_l3 = module.positional_embedding_l3.to(self.device).contiguous() if self.label_query else None
         self.max_pos_len = min(t.shape[0] for t in (module.pos_embedding[0], self.pe, self.pe_depth, self.pe_l3) if t is not None)
-        self.ws = ops.GemmWorkspace(self.device)
         self.dropout_enabled = bool(getattr(module, "r3d_dropout_enabled", True))
-        self.erank_weight = 0.0                # (the rank penalty is defined on the fuser's tokens; this model has no fuser)
-        self.defer_tail = False
-        self.dur_den = None
-        self.grad_hook = None
-        self.tp = None
-        self._drop_ready = None
-        self._init_step_state()
 
-    def _shape(self, B, S, train):
-        key = (B, S, bool(train))
-        if key not in self.shapes:
-            check_query_clip_shape(S, self.H, self.heads, self.max_pos_len, train, self.long_clips)     # (before anything is enqueued)
-            self.shapes[key] = _Shape(self, B, S, train)
-        return self.shapes[key]
+    def _admit(self, B, S, train):
+        check_query_clip_shape(S, self.H, self.heads, self.max_pos_len, train, self.long_clips)
 
     # ------------------------------------------------------------------------------------------------------
     def forward(self, feats, depth, labels, mode="train", training=False, need_grad=True):
@@ -266,14 +251,6 @@ class UnsupDepthEngine(ComposedEngine):
         ops.rowmod_sum(w.d_dep_pre, 1, a.g("depth_projection.bias").view(1, H))
 
     # ------------------------------------------------------------------------------------------------------
-    def adamw(self, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, tick_dropout=False, ticked=False,
-              skip_depth=False, prefill_dropout=False, before_flat=None):
-        """One fused launch over the live prefix of the arena (main_darai.py:135; train_proposed_depth.py:215)."""
-        self.set_lr(lr)
-        if not ticked:
-            ops.tick(self.step_t, self.drop_offset if tick_dropout else None)
-        self._adamw_flat(weight_decay, betas, eps, grad_scale)
-
     def train_step(self, feats, depth, past_label, target_dur, target, lr, weight_decay, training=True):
         """forward + losses + backward + AdamW, all enqueued, no host sync.  Returns (loss[4], counts[4]) on device."""
         self.forward(feats, depth, past_label, "train", training)

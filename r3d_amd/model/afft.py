@@ -16,6 +16,7 @@ Same class names, constructor and forward signature; the parameters are holders 
 libr3d_hip.so (r3d_amd/engine_afft.py: the plain front's launches + csrc/afft.hip, the pooled-head chain)."""
 import torch
 
+from ._bridge import arena_grads, logit_grads_in
 from . import futr_safuser_depth as _plain
 from . import futr_safuser_tokenfusion as _base
 
@@ -66,14 +67,6 @@ class _PooledForward(torch.autograd.Function):
             raise RuntimeError("r3d_amd: backward() must follow the forward() it belongs to (the engine keeps one "
                                "set of saved activations per shape)")
         w, K = eng.last["w"], eng.K
-        if d_act is None:
-            w.d_actdur[:, :K].zero_()
-        else:
-            w.d_actdur[:, :K].copy_(d_act.reshape(-1, K))
-        if d_dur is None:
-            w.d_actdur[:, K].zero_()
-        else:
-            w.d_actdur[:, K].copy_(d_dur.reshape(-1))
+        logit_grads_in(w, K, d_act, d_dur, None)
         eng.backward(d_actdur=w.d_actdur)
-        grads = [eng.arena.g(n).clone() if eng.arena.is_live(n) else None for n in ctx.names]
-        return (None,) * 7 + tuple(grads)
+        return (None,) * 7 + arena_grads(eng, ctx.names)

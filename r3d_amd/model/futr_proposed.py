@@ -9,18 +9,19 @@ outputs, :38).  The arithmetic runs in libr3d_hip.so through r3d_amd.engine_unsu
 here are parameter holders.  Its training loop in the reference is train/train_unsupervised.py (out of scope, SURVEY.md
 section 2): this module is driven through autograd (any torch loss on the outputs + ``.backward()``)."""
 import math
-import weakref
 
 import torch
 from torch import nn
 
 from ..engine_unsup import UnsupDepthEngine
+from ._bridge import EngineOwner
 from .futr_safuser_tokenfusion import _Transformer, _PositionalEncoding
 
 
-class FUTR(nn.Module):
+class FUTR(EngineOwner, nn.Module):
     """FUTR(n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
     num_decoder_layers=6, query_num=48) -- model/futr_proposed.py:20-60."""
+    _engine_param, _engine_cls = "input_embed.weight", UnsupDepthEngine
 
     def __init__(self, n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
                  num_decoder_layers=6, query_num=48):
@@ -59,23 +60,6 @@ class FUTR(nn.Module):
         pe[:, 0::2] = torch.sin(position * div_term)
         pe[:, 1::2] = torch.cos(position * div_term)
         self.positional_embedding_l3 = pe
-        self._engine = None
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None
-        return super()._apply(fn, *a, **k)
-
-    def engine(self):
-        dev = self.input_embed.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("r3d_amd.FUTR computes only on an MI355X through libr3d_hip.so; move the model to the "
-                               "GPU with .to('cuda') (there is deliberately no CPU path).")
-        if self._engine is None or self._engine.device != dev:
-            self._engine = UnsupDepthEngine(self, dev)
-            ref = weakref.ref(self._engine)
-            for p in self.parameters():
-                p._r3d_engine = ref
-        return self._engine
 
     def forward(self, inputs, query, mode="train", epoch=0, idx=0):
         if mode == "train":

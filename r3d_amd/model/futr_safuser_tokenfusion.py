@@ -9,12 +9,12 @@ on a non-HIP device forward() raises (there is no CPU path).
 """
 import copy
 import math
-import weakref
 
 import torch
 from torch import nn
 
 from ..engine import FusionEngine
+from ._bridge import EngineOwner, arena_grads, logit_grads_in
 
 
 # ---- parameter holders with the reference's module tree (model/extras/transformerblock.py, transformer.py) ----------
@@ -105,7 +105,7 @@ class CMFuser(nn.Module):
         self.fusion_conv = nn.Conv2d(in_channels=2, out_channels=1, kernel_size=1)
 
 
-class FUTR(nn.Module):
+class FUTR(EngineOwner, nn.Module):
     """FUTR(n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
     num_decoder_layers=6, query_num=49) -- model/futr_safuser_tokenfusion.py:103-152."""
 
@@ -113,6 +113,7 @@ class FUTR(nn.Module):
     # hooks of the models that share this constructor and forward (model/afft.py: no 'seg' output, fc_seg only with args.seg)
     _out_names = ("duration", "action", "seg")
     _seg_optional = False
+    _engine_param = "depth_projection.weight"
 
     @staticmethod
     def _engine_cls():
@@ -167,24 +168,6 @@ class FUTR(nn.Module):
         self.depth_projection = nn.Linear(depth_pixels, hidden_dim)
         nn.init.xavier_uniform_(self.depth_projection.weight)
         self.depth_layernorm = nn.LayerNorm(hidden_dim)
-        self._engine = None
-
-    # ---- engine life cycle ------------------------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        self._engine = None                     # .to()/.cuda() re-creates parameter storage; re-flatten lazily
-        return super()._apply(fn, *a, **k)
-
-    def engine(self):
-        dev = self.depth_projection.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("r3d_amd.FUTR computes only on an MI355X through libr3d_hip.so; move the model to the "
-                               "GPU with .to('cuda') (there is deliberately no CPU path).")
-        if self._engine is None or self._engine.device != dev:
-            self._engine = self._engine_cls()(self, dev)
-            ref = weakref.ref(self._engine)
-            for p in self.parameters():
-                p._r3d_engine = ref              # lets r3d_amd.optim.FlatAdamW find the arena behind its parameters
-        return self._engine
 
     # ---- forward ------------------------------------------------------------------------------------------------
     def forward(self, inputs, depth_features, mode="train", epoch=0, idx=0):
@@ -224,21 +207,8 @@ class _FusedForward(torch.autograd.Function):
         if eng.last is not ctx.token:
             raise RuntimeError("r3d_amd: backward() must follow the forward() it belongs to (the engine keeps one "
                                "set of saved activations per shape)")
-        w = eng.last["w"]
-        K = eng.K
-        if d_act is None:
-            w.d_actdur[:, :K].zero_()
-        else:
-            w.d_actdur[:, :K].copy_(d_act.reshape(-1, K))
-        if d_dur is None:
-            w.d_actdur[:, K].zero_()
-        else:
-            w.d_actdur[:, K].copy_(d_dur.reshape(-1))
-        if d_seg is None:
-            w.d_seg.zero_()
-        else:
-            w.d_seg.copy_(d_seg.reshape(-1, K))
+        w, K = eng.last["w"], eng.K
+        logit_grads_in(w, K, d_act, d_dur, d_seg)
         eng.backward()
-        grads = [eng.arena.g(n).clone() if eng.arena.is_live(n) else None for n in ctx.names]
-        return (None,) * 7 + tuple(grads)
+        return (None,) * 7 + arena_grads(eng, ctx.names)
 

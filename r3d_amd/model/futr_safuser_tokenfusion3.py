@@ -27,6 +27,7 @@ The modules below are parameter holders; all arithmetic runs in HIP through r3d_
 import torch
 from torch import nn
 
+from ._bridge import arena_grads, logit_grads_in
 from .cmfuser3 import CMFuser3
 from .futr_safuser_tokenfusion import FUTR as _FUTR2
 
@@ -91,18 +92,6 @@ class _FusedForward3(torch.autograd.Function):
             raise RuntimeError("r3d_amd: backward() must follow the forward() it belongs to (the engine keeps one "
                                "set of saved activations per shape)")
         w, K = eng.last["w"], eng.K
-        if d_act is None:
-            w.d_actdur[:, :K].zero_()
-        else:
-            w.d_actdur[:, :K].copy_(d_act.reshape(-1, K))
-        if d_dur is None:
-            w.d_actdur[:, K].zero_()
-        else:
-            w.d_actdur[:, K].copy_(d_dur.reshape(-1))
-        if d_seg is None:
-            w.d_seg.zero_()
-        else:
-            w.d_seg.copy_(d_seg.reshape(-1, K))
+        logit_grads_in(w, K, d_act, d_dur, d_seg)
         eng.backward()
-        grads = [eng.arena.g(n).clone() if eng.arena.is_live(n) else None for n in ctx.names]
-        return (None,) * 8 + tuple(grads)
+        return (None,) * 8 + arena_grads(eng, ctx.names)

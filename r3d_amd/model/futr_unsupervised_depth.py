@@ -12,18 +12,19 @@ Reference quirk, documented not emulated: in any mode but 'train' the reference'
 feature tensor (:91) while its own validate() (train_proposed_depth.py:72) passes the (features, labels) tuple, so the
 reference crashes there.  This module accepts either.
 """
-import weakref
 
 import torch
 from torch import nn
 
 from ..engine_unsup import UnsupDepthEngine
+from ._bridge import EngineOwner, arena_grads, logit_grads_in
 from .futr_safuser_tokenfusion import _Transformer, _PositionalEncoding
 
 
-class FUTR(nn.Module):
+class FUTR(EngineOwner, nn.Module):
     """FUTR(n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
     num_decoder_layers=6, query_num=49) -- model/futr_unsupervised_depth.py:20-66."""
+    _engine_param, _engine_cls = "depth_projection.weight", UnsupDepthEngine
 
     def __init__(self, n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
                  num_decoder_layers=6, query_num=49, depth_pixels=160 * 120):
@@ -64,23 +65,6 @@ class FUTR(nn.Module):
         self.depth_projection = nn.Linear(depth_pixels, hidden_dim)                                         # :59
         nn.init.xavier_uniform_(self.depth_projection.weight)
         self.depth_layernorm = nn.LayerNorm(hidden_dim)
-        self._engine = None
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None
-        return super()._apply(fn, *a, **k)
-
-    def engine(self):
-        dev = self.depth_projection.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("r3d_amd.FUTR computes only on an MI355X through libr3d_hip.so; move the model to the "
-                               "GPU with .to('cuda') (there is deliberately no CPU path).")
-        if self._engine is None or self._engine.device != dev:
-            self._engine = UnsupDepthEngine(self, dev)
-            ref = weakref.ref(self._engine)
-            for p in self.parameters():
-                p._r3d_engine = ref
-        return self._engine
 
     def forward(self, inputs, depth_features, mode="train", epoch=0, idx=0):
         if mode == "train":
@@ -117,18 +101,6 @@ class _Forward(torch.autograd.Function):
         if eng.last is not ctx.token:
             raise RuntimeError("r3d_amd: backward() must follow the forward() it belongs to")
         w, K = eng.last["w"], eng.K
-        if d_act is None:
-            w.d_actdur[:, :K].zero_()
-        else:
-            w.d_actdur[:, :K].copy_(d_act.reshape(-1, K))
-        if d_dur is None:
-            w.d_actdur[:, K].zero_()
-        else:
-            w.d_actdur[:, K].copy_(d_dur.reshape(-1))
-        if d_seg is None:
-            w.d_seg.zero_()
-        else:
-            w.d_seg.copy_(d_seg.reshape(w.d_seg.shape))
+        logit_grads_in(w, K, d_act, d_dur, d_seg)
         eng.backward()
-        grads = [eng.arena.g(n).clone() if eng.arena.is_live(n) else None for n in ctx.names]
-        return (None,) * 7 + tuple(grads)
+        return (None,) * 7 + arena_grads(eng, ctx.names)

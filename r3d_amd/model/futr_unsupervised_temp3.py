@@ -11,18 +11,19 @@ reference.  transformer.encoder.* and query_attention.* are constructed (state_d
 The arithmetic runs in libr3d_hip.so through r3d_amd.engine_l3.L3Engine; modules here are parameter holders.
 r3d_amd.train_unsupervised.train() drives the engine's fused step; any other torch loss on the outputs goes through autograd."""
 import math
-import weakref
 
 import torch
 from torch import nn
 
 from ..engine_l3 import L3Engine
+from ._bridge import EngineOwner, arena_grads, logit_grads_in
 from .futr_safuser_tokenfusion import _Transformer, _PositionalEncoding
 
 
-class FUTR(nn.Module):
+class FUTR(EngineOwner, nn.Module):
     """FUTR(n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
     num_decoder_layers=6, query_num=49) -- model/futr_unsupervised_temp3.py:20-60."""
+    _engine_param, _engine_cls = "input_embed.weight", L3Engine
 
     def __init__(self, n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
                  num_decoder_layers=6, query_num=49):
@@ -64,23 +65,6 @@ class FUTR(nn.Module):
         pe[:, 0::2] = torch.sin(position * div_term)
         pe[:, 1::2] = torch.cos(position * div_term)
         self.positional_embedding_l3 = pe
-        self._engine = None
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None
-        return super()._apply(fn, *a, **k)
-
-    def engine(self):
-        dev = self.input_embed.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("r3d_amd.FUTR computes only on an MI355X through libr3d_hip.so; move the model to the "
-                               "GPU with .to('cuda') (there is deliberately no CPU path).")
-        if self._engine is None or self._engine.device != dev:
-            self._engine = L3Engine(self, dev)
-            ref = weakref.ref(self._engine)
-            for p in self.parameters():
-                p._r3d_engine = ref
-        return self._engine
 
     def forward(self, inputs, query, mode="train", epoch=0, idx=0):
         if mode == "train":
@@ -116,11 +100,10 @@ class _Forward(torch.autograd.Function):
         if eng.last is not ctx.token:
             raise RuntimeError("r3d_amd: backward() must follow the forward() it belongs to")
         w, K = eng.last["w"], eng.K
-        for dst, src in ((w.d_actdur[:, :K], d_act), (w.d_actdur[:, K], d_dur), (w.d_seg, d_seg), (w.d_l3log, d_l3)):
-            if src is None:
-                dst.zero_()
-            else:
-                dst.copy_(src.reshape(dst.shape))
+        logit_grads_in(w, K, d_act, d_dur, d_seg)
+        if d_l3 is None:
+            w.d_l3log.zero_()
+        else:
+            w.d_l3log.copy_(d_l3.reshape(w.d_l3log.shape))
         eng.backward()
-        grads = [eng.arena.g(n).clone() if eng.arena.is_live(n) else None for n in ctx.names]
-        return (None,) * 6 + tuple(grads)
+        return (None,) * 6 + arena_grads(eng, ctx.names)

@@ -16,12 +16,12 @@ engine's arena.  Nothing here calls nn.LSTM or MIOpen.
 Outside train mode the reference takes the bare feature tensor (:79); the (features, labels) tuple is accepted too.
 """
 import math
-import weakref
 
 import torch
 from torch import nn
 
 from ..engine_rnn import RnnEngine
+from ._bridge import EngineOwner, arena_grads, logit_grads_in
 from .futr_safuser_tokenfusion import _Transformer, _PositionalEncoding
 
 
@@ -46,9 +46,10 @@ class _LSTMParams(nn.Module):
             nn.init.uniform_(p, -stdv, stdv)
 
 
-class FUTR(nn.Module):
+class FUTR(EngineOwner, nn.Module):
     """FUTR(n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
     num_decoder_layers=6, query_num=19) -- model/rnn.py:17-60."""
+    _engine_param, _engine_name, _engine_cls = "input_embed.weight", "r3d_amd.model.rnn.FUTR", RnnEngine
 
     def __init__(self, n_class, hidden_dim, src_pad_idx, device, args, n_query=8, n_head=8, num_encoder_layers=6,
                  num_decoder_layers=6, query_num=19):
@@ -80,23 +81,6 @@ class FUTR(nn.Module):
         self.pos_embedding = nn.Parameter(torch.zeros(1, args.max_pos_len, hidden_dim))                    # :49 (unused)
         nn.init.xavier_uniform_(self.pos_embedding)
         self.pos_enc = _PositionalEncoding(hidden_dim)                                                      # :52 (unused)
-        self._engine = None
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None
-        return super()._apply(fn, *a, **k)
-
-    def engine(self):
-        dev = self.input_embed.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("r3d_amd.model.rnn.FUTR computes only on an MI355X through libr3d_hip.so; move the model to "
-                               "the GPU with .to('cuda') (there is deliberately no CPU path).")
-        if self._engine is None or self._engine.device != dev:
-            self._engine = RnnEngine(self, dev)
-            ref = weakref.ref(self._engine)
-            for p in self.parameters():
-                p._r3d_engine = ref
-        return self._engine
 
     def forward(self, inputs, mode="train", epoch=0, idx=0):
         if mode == "train":
@@ -130,18 +114,6 @@ class _Forward(torch.autograd.Function):
         if eng.last is not ctx.token:
             raise RuntimeError("r3d_amd: backward() must follow the forward() it belongs to")
         w, K = eng.last["w"], eng.K
-        if d_act is None:
-            w.d_actdur[:, :K].zero_()
-        else:
-            w.d_actdur[:, :K].copy_(d_act.reshape(-1, K))
-        if d_dur is None:
-            w.d_actdur[:, K].zero_()
-        else:
-            w.d_actdur[:, K].copy_(d_dur.reshape(-1))
-        if d_seg is None:
-            w.d_seg.zero_()
-        else:
-            w.d_seg.copy_(d_seg.reshape(w.d_seg.shape))
+        logit_grads_in(w, K, d_act, d_dur, d_seg)
         eng.backward(d_supcon=None if d_sup is None else d_sup.to(torch.float32))
-        grads = [eng.arena.g(n).clone() if eng.arena.is_live(n) else None for n in ctx.names]
-        return (None,) * 4 + tuple(grads)
+        return (None,) * 4 + arena_grads(eng, ctx.names)

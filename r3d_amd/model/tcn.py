@@ -15,12 +15,11 @@ Initialisation, as the reference leaves it: ``init_weights()`` writes N(0, 0.01)
 ``weight_norm`` is a derived attribute, so ``weight_v`` / ``weight_g`` keep nn.Conv1d's default initialisation -- but the
 call still draws from the generator, and so does this file.  ``downsample.weight`` really is N(0, 0.01).
 """
-import weakref
-
 import torch
 from torch import nn
 
 from ..engine_tcn import TcnEngine, TCN_IN, TCN_CHANNELS, TCN_DROP_P
+from ._bridge import EngineOwner, arena_grads
 
 _ONLY_WHOLE = ("r3d_amd.model.tcn: only MustafaNet1DTCN.forward computes (one fused engine on the GPU); the blocks are "
                "parameter holders")
@@ -98,8 +97,9 @@ class TemporalConvNet1D(nn.Module):
         raise NotImplementedError(_ONLY_WHOLE)
 
 
-class MustafaNet1DTCN(nn.Module):
+class MustafaNet1DTCN(EngineOwner, nn.Module):
     """MustafaNet1DTCN(num_classes=15, anticipated_frames=8); forward(x [B, S, 2048]) -> [B, anticipated_frames, num_classes]."""
+    _engine_param, _engine_name, _engine_cls = "regression.weight", "r3d_amd.model.tcn.MustafaNet1DTCN", TcnEngine
 
     def __init__(self, num_classes=15, anticipated_frames=8):
         super().__init__()
@@ -108,23 +108,6 @@ class MustafaNet1DTCN(nn.Module):
         self.tcn_local = TemporalConvNet1D(num_inputs=TCN_IN, num_channels=list(TCN_CHANNELS), kernel_size=3,
                                            dropout=TCN_DROP_P)
         self.regression = nn.Conv1d(in_channels=TCN_CHANNELS[-1], out_channels=num_classes * anticipated_frames, kernel_size=1)
-        self._engine = None
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None
-        return super()._apply(fn, *a, **k)
-
-    def engine(self):
-        dev = self.regression.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("r3d_amd.model.tcn.MustafaNet1DTCN computes only on an MI355X through libr3d_hip.so; move the "
-                               "model to the GPU with .to('cuda') (there is deliberately no CPU path).")
-        if self._engine is None or self._engine.device != dev:
-            self._engine = TcnEngine(self, dev)
-            ref = weakref.ref(self._engine)
-            for p in self.parameters():
-                p._r3d_engine = ref
-        return self._engine
 
     def forward(self, x):
         from ..engine_tcn import check_tcn_shape
@@ -156,4 +139,4 @@ class _Forward(torch.autograd.Function):
         if eng.last is not ctx.token:
             raise RuntimeError("r3d_amd: backward() must follow the forward() it belongs to")
         eng.backward(d_logits=d_out.to(torch.float32).contiguous())
-        return (None,) * 4 + tuple(eng.arena.g(n).clone() for n in ctx.names)
+        return (None,) * 4 + arena_grads(eng, ctx.names)

@@ -40,7 +40,7 @@ def shard_range(n_items, rank, world):
 
 def refuse_tall_route(engine, who):
     """The tall rank route (engine.erank_route = "tall") has only been run on one GPU: not offered under `who`."""
-    if getattr(engine, "erank_route", "jacobi") == "tall":
+    if engine.erank_route == "tall":
         raise ValueError(f"erank_route 'tall' with {who}: the tall rank route runs on one GPU; use erank_route 'jacobi'")
 
 
@@ -275,12 +275,12 @@ class DataParallelStep:
         engine.grad_hook = self._on_stage
         engine.score_allreduce = self._scores
         self.comm_override = None         # RcclStep: exchanges issued from inside the step go through its communicator
-        if getattr(engine, "bn", False) and sync_bn and self.active:
+        if engine.bn and sync_bn and self.active:
             engine.bn_sync = SyncBatchNorm(self)
         if self.active:
             engine.dur_den = self._den
         self.tp = None
-        if pixel_shard and self.active and getattr(engine, "vary", False):
+        if pixel_shard and self.active and engine.vary:
             raise NotImplementedError("the activation-magnitude fuser variant (futr_safuser_tokenfusion_vary) runs data "
                                       "parallel with replicated weights only: no pixel-sharded depth projection")
         if pixel_shard and self.active:
@@ -319,7 +319,7 @@ class DataParallelStep:
     def _small_live(self):
         """Floats of the small bucket that can be non-zero: pos_embedding [1, 2000, H] sits last in it and only its first
         S rows (the clip length of this step) receive a gradient -- the rest is exact zeros on every rank."""
-        a, last = self.eng.arena, getattr(self.eng, "last", None)
+        a, last = self.eng.arena, self.eng.last
         offs = getattr(a, "offsets", None)
         if not last or not offs or "pos_embedding" not in offs:
             return self.small.numel()
@@ -400,7 +400,7 @@ class RcclStep:
     def __init__(self, dp, comm, comm_side, lr, weight_decay, fuse_adam=False):
         self.dp, self.eng, self.tp = dp, dp.eng, dp.tp
         refuse_tall_route(self.eng, "the RCCL step")
-        if getattr(self.eng, "vary", False):
+        if self.eng.vary:
             raise NotImplementedError("the activation-magnitude fuser variant (futr_safuser_tokenfusion_vary) all-reduces "
                                       "its selection scores through torch.distributed inside the step; no one-graph RCCL step")
         self.comm, self.side_comm = comm, comm_side

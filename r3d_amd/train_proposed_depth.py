@@ -77,7 +77,7 @@ def _graph_key(eng, hyper):
     """What a captured step depends on besides its batch shape: the AdamW hyper-parameters and the engine's high-water
     mark of pos_embedding gradient rows (a step clears rows [S, mark) as the mark stood AT CAPTURE, so a longer batch seen
     since then forces a re-capture)."""
-    return (hyper, getattr(eng, "pos_grad_rows", 0))
+    return (hyper, eng.pos_grad_rows)
 
 
 class _GraphedSteps:
@@ -100,8 +100,7 @@ class _GraphedSteps:
     def step(self, batch, lr, hyper, training):
         eng = self.eng
         key = tuple(tuple(t.shape) for t in batch) + (bool(training), float(eng.erank_weight),
-                                                      str(getattr(eng, "erank_route", "jacobi")),
-                                                      str(getattr(eng, "erank_fold", None)))
+                                                      str(eng.erank_route), str(eng.erank_fold))
         st = self.shapes.get(key)
         if st is None:
             st = self.shapes[key] = dict(buf=[torch.empty_like(t) for t in batch], seen=0, graph=None, hyper=None)
@@ -187,14 +186,14 @@ class _GraphedSteps:
         wd, betas, eps = hyper
         # forward -> losses -> backward back to back: the decoder tail, the losses and the tail's backward are one launch
         # (defer_tail), and the loss statistics -- with their epoch sums -- are reduced by one workgroup of the AdamW launch
-        fused = hasattr(eng, "defer_loss_reduce")            # (the depth-as-query engine keeps its separate launches)
+        fused = eng.fused_loss_flow                          # (the depth-as-query engine keeps its separate launches)
         if fused:
             keep = (eng.defer_tail, eng.defer_loss_reduce, eng.loss_acc)
             eng.defer_tail, eng.defer_loss_reduce, eng.loss_acc = True, True, (self.acc_loss, self.acc_cnt)
         try:
             eng.forward(feats, depth, lab, "train", training=training, **kw)
             loss, counts = eng.losses(lab, tgt, dur, tick=True)
-            folded = getattr(eng, "_loss_pending", None) is not None
+            folded = eng._loss_pending is not None
         finally:
             if fused:
                 eng.defer_tail, eng.defer_loss_reduce, eng.loss_acc = keep
@@ -375,7 +374,7 @@ def _print_erank(eng):
     tall one decomposes them."""
     from .erank import effective_rank
     fused = eng.last["w"].fused
-    tall = getattr(eng, "erank_route", "jacobi") == "tall" and fused.shape[0] >= fused.shape[1]
+    tall = eng.erank_route == "tall" and fused.shape[0] >= fused.shape[1]
     print("effective rank of fused tokens: %.3f" % float(effective_rank(fused, route="tall" if tall else "auto")))
 
 
@@ -416,7 +415,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         rank_accs = rankstream.attach(core)          # (ValueError for the query models: no fused token matrix)
         rankstream.detach(core)                      # fed by validate()'s forwards only
     eng.erank_weight = float(getattr(args, "erank_weight", 0.0))
-    if hasattr(eng, "erank_route"):      # (the engines without a fused token matrix refuse the penalty itself)
+    if eng.rank_penalty:                 # (the engines without a fused token matrix refuse the penalty itself)
         eng.erank_route = str(getattr(args, "erank_route", "jacobi"))
     print("Training Start")
     best_val_loss = float("inf")
@@ -429,7 +428,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     rs = None
     # the activation-magnitude variant all-reduces its selection scores (and their row count, read on the host) inside the
     # step: with more than one rank its steps run eagerly, without the RCCL one-graph step
-    vary_dp = bool(getattr(eng, "vary", False) and dp is not None and dp.active)
+    vary_dp = bool(eng.vary and dp is not None and dp.active)
     if (dp is not None and dp.active and getattr(args, "graph_steps", True) and not getattr(args, "torch_collectives", False)
             and not vary_dp):
         g0 = optimizer.param_groups[0]
@@ -501,7 +500,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
             eng.forward(features, depth_features, past_label, "train", training=model.training, **kw)
             fused_opt = isinstance(optimizer, FlatAdamW)
             loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, tick=fused_opt)
-            fuse = bool(fused_opt and dp is None and hasattr(eng, "depth_adamw_fusable") and eng.depth_adamw_fusable())
+            fuse = bool(fused_opt and dp is None and eng.depth_adamw_fusable())
             eng.backward(fused_adamw=dict(lr=g["lr"], weight_decay=g["weight_decay"], betas=g["betas"], eps=g["eps"])
                          if fuse else None, adamw_next=fused_opt and dp is None)
             if dp is not None:

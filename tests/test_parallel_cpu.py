@@ -11,6 +11,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import futr_oracle as O, synth
+from r3d_amd.engine_base import EngineBase
 from tests.helpers import load_fixture, fixture_params
 
 
@@ -33,7 +34,7 @@ class _FakeArena:
         return self.grads[int(self.offs[i]):int(self.offs[i + 1])]
 
 
-class _FakeEngine:
+class _FakeEngine(EngineBase):              # (the declared surface with its defaults; the wrapper sets its hooks)
     def __init__(self, arena):
         self.arena = arena
         self.grad_hook = None
@@ -139,7 +140,7 @@ class _TpArena:
         return self.params[o:o + k].view(shp)
 
 
-class _TpEngine:
+class _TpEngine(EngineBase):
     def __init__(self, H, P):
         self.H, self.P, self.device, self.tp = H, P, torch.device("cpu"), None
         self.arena = _TpArena(H, P, 7)
