@@ -817,6 +817,23 @@ int r3d_lstm_layer_fwd(const float* gin, int ldgin, const float* whh_fwd, const 
 int r3d_lstm_layer_bwd(const float* dy, int lddy, const float* whh_fwd, const float* whh_rev, const float* gates, int ldgates,
                        const float* cell, int ldcell, float* dg, int lddg, int B, int S, int H, void* stream);
 
+/* ---- the same layer, stepwise: one launch per time step, W_hh spread over the chip (csrc/lstm_steps.hip), for hidden sizes
+ * whose W_hh no single workgroup holds.  Same tensors and layouts as above, so the GEMMs around the recurrence are unchanged.
+ * r3d_lstm_steps_supported: 8 <= H <= 1024, H % 8 == 0.
+ * r3d_lstm_steps_ws_floats: the backward's workspace: the dc carry [B, 2h] followed by the transposed W_hh [2][h][4h]
+ *   (B H + 2 H H floats); R3D_EINVAL for a shape the route does not take.
+ * r3d_lstm_steps_layer_fwd / _bwd: one call enqueues the S step launches of a layer (the backward one transposing launch
+ *   first), each checked; nothing waits across workgroups, so the calls can be captured in a hipGraph.  gin, gates, y, dg, ws,
+ *   W_hh and b_hh must be 16-byte aligned and ldgin, ldgates, ldy, lddg multiples of 4 (R3D_EALIGN otherwise). */
+int r3d_lstm_steps_supported(int H);
+int64_t r3d_lstm_steps_ws_floats(int B, int H);
+int r3d_lstm_steps_layer_fwd(const float* gin, int ldgin, const float* whh_fwd, const float* whh_rev, const float* bhh_fwd,
+                             const float* bhh_rev, float* y, int ldy, float* gates, int ldgates, float* cell, int ldcell,
+                             float* hprev, int ldhprev, int B, int S, int H, void* stream);
+int r3d_lstm_steps_layer_bwd(const float* dy, int lddy, const float* whh_fwd, const float* whh_rev, const float* gates,
+                             int ldgates, const float* cell, int ldcell, float* dg, int lddg, int B, int S, int H, float* ws,
+                             void* stream);
+
 /* ---- temporal convolution (reference model/tcn.py: weight_norm(nn.Conv1d(C_in, C_out, 3, padding=2d, dilation=d)) + Chomp1d)
  * Activations are [rows = B*S, C] row-major, a clip's S frames consecutive; tap j of weight_v [C_out, C_in, 3] reads frame
  * t - (2 - j) d of the same clip (zeros before frame 0).  The three products are fp32-MFMA tile GEMMs whose operand loader

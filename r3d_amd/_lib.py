@@ -321,6 +321,10 @@ _SIGNATURES = {
     "r3d_lstm_supported": ([_I], C.c_int),
     "r3d_lstm_layer_fwd": ([_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
     "r3d_lstm_layer_bwd": ([_P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_lstm_steps_supported": ([_I], C.c_int),
+    "r3d_lstm_steps_ws_floats": ([_I, _I], C.c_int64),
+    "r3d_lstm_steps_layer_fwd": ([_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
+    "r3d_lstm_steps_layer_bwd": ([_P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P], C.c_int),
     "r3d_tconv_supported": ([_I, _I, _I, _I, _I], C.c_int),
     "r3d_tconv_ws_floats": ([_I, _I], C.c_int64),
     "r3d_tconv_wnorm": ([_P, _P, _I, _I, _P, _P, _P], C.c_int),

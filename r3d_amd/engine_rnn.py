@@ -11,6 +11,8 @@ Same flat arenas, C ABI and method surface (forward / losses / backward / adamw 
 the graphed steps of train_proposed_depth drive it.  Per layer the input projection of both directions is ONE GEMM (the
 arena keeps weight_ih_l<k> and weight_ih_l<k>_reverse adjacent, likewise bias_ih), the recurrence is ONE launch of
 csrc/lstm.hip (both directions), and the backward's dW_ih / dX are one GEMM each, dW_hh (+ d b_hh) one per direction.
+Past hidden 256 (opts --wide_rnn) the recurrence is csrc/lstm_steps.hip instead: one launch per time step, W_hh spread over
+the chip, the same tensors in the same layouts, so everything around it is unchanged (lstm_route picks the kernels).
 """
 import torch
 
@@ -21,6 +23,8 @@ from .engine_base import EngineBase
 EXCLUDE_CLASS_IDX = 120         # NTU's UNDEFINED class, hard-coded at train/train_unimodal.py:102,198,212
 POOL_ROWS = 8                   # F.adaptive_avg_pool1d(tgt, 8) (model/rnn.py:97)
 RNN_MIN_H, RNN_MAX_H = 8, 256   # the recurrence kernels' range (csrc/lstm.hip: W_hh of one direction in registers)
+RNN_WIDE_MAX_H = 1024           # with --wide_rnn: the stepwise recurrence (csrc/lstm_steps.hip: one launch per time step)
+SUPCON_MAX_H = 256              # the supervised contrastive kernel's column limit (csrc/supcon.hip)
 
 SUPCON_BASE_T = 0.07            # SupConLoss's default base_temperature (loss/spc.py:69); the entry scripts pass temperature only
 
@@ -31,19 +35,41 @@ def is_live(name):
     return name.startswith(RNN_LIVE_PREFIXES)
 
 
-def check_rnn_shape(H, n_query=POOL_ROWS, erank_weight=0.0):
-    """Raises ValueError unless the engine runs this model: hidden H in the recurrence kernels' range, n_query == 8 (the
-    reference pools to 8 rows whatever n_query is, so its targets of n_query rows would not match the 8 outputs), and no
-    effective-rank penalty (defined on a fuser's token matrix; this model has none).  Host-only, nothing is enqueued."""
-    if not (RNN_MIN_H <= H <= RNN_MAX_H) or H % 8:
+def lstm_route(H, wide):
+    """Which recurrence kernels run hidden H: "registers" (csrc/lstm.hip) wherever they take H, whatever the flag, so a run
+    at hidden <= 256 launches the same kernels with or without --wide_rnn; "steps" (csrc/lstm_steps.hip) for wider H with the
+    flag; None (refused) otherwise."""
+    if ops.lstm_supported(H):
+        return "registers"
+    if wide and ops.lstm_steps_supported(H):
+        return "steps"
+    return None
+
+
+def check_rnn_shape(H, n_query=POOL_ROWS, erank_weight=0.0, wide=False, supcon_weight=0.0):
+    """Raises ValueError unless the engine runs this model: hidden H in the recurrence kernels' range (up to RNN_WIDE_MAX_H
+    with wide, opts --wide_rnn), n_query == 8 (the reference pools to 8 rows whatever n_query is, so its targets of n_query
+    rows would not match the 8 outputs), no effective-rank penalty (defined on a fuser's token matrix; this model has none)
+    and no supervised contrastive term past its kernel's width.  Host-only, nothing is enqueued."""
+    if wide:
+        if not (RNN_MIN_H <= H <= RNN_WIDE_MAX_H) or H % 8:
+            raise ValueError(f"hidden {H}: with --wide_rnn the LSTM recurrence kernels take {RNN_MIN_H} <= hidden <= "
+                             f"{RNN_WIDE_MAX_H} with hidden % 8 == 0")
+    elif not (RNN_MIN_H <= H <= RNN_MAX_H) or H % 8:
+        hint = ""
+        if RNN_MAX_H < H <= RNN_WIDE_MAX_H and H % 8 == 0:
+            hint = "; the stepwise recurrence runs this hidden size: --wide_rnn"
         raise ValueError(f"hidden {H}: the LSTM recurrence kernels take {RNN_MIN_H} <= hidden <= {RNN_MAX_H} with hidden % 8 "
-                         f"== 0 (W_hh of one direction, 2 hidden x hidden / 2 floats, is held in registers)")
+                         f"== 0 (W_hh of one direction, 2 hidden x hidden / 2 floats, is held in registers){hint}")
     if n_query != POOL_ROWS:
         raise ValueError(f"n_query {n_query}: the RNN model pools to {POOL_ROWS} rows (model/rnn.py:97), so its anticipation "
                          f"outputs only match targets of n_query == {POOL_ROWS} rows")
     if erank_weight:
         raise ValueError(f"erank_weight {erank_weight}: the effective-rank penalty needs a fuser's token matrix; the RNN "
                          f"model has none")
+    if supcon_weight and H > SUPCON_MAX_H:
+        raise ValueError(f"supcon_weight {supcon_weight} at hidden {H}: the supervised contrastive kernel takes rows of at "
+                         f"most {SUPCON_MAX_H} columns (csrc/supcon.hip), so --supcon_weight needs hidden <= {SUPCON_MAX_H}")
 
 
 def _arena_order(named):
@@ -87,19 +113,23 @@ class _Shape:
             self.dg = f(N, 4 * H)
             self.d_x0, self.d_x, self.d_pre = f(N, H), f(N, H), f(N, H)
             self.sc_ws, self.sc_loss = f(ops.supcon_ws_floats(N)), torch.zeros(1, dtype=torch.float32, device=dev)
+            if eng.steps:               # the stepwise backward's dc carry and transposed W_hh
+                self.lstm_ws = f(ops.lstm_steps_ws_floats(B, H))
 
 
 class RnnEngine(EngineBase):
     _Shape = _Shape
+    use_lstm_steps = None           # None: routed by lstm_route(); True: the stepwise kernels at any admitted hidden size
 
     def __init__(self, module, device):
-        check_rnn_shape(module.hidden_dim, module.n_query)          # (before anything is enqueued)
+        self.wide = bool(getattr(module, "r3d_wide_rnn", False))    # (opts --wide_rnn)
+        check_rnn_shape(module.hidden_dim, module.n_query, wide=self.wide)     # (before anything is enqueued)
         self.H, self.Q, self.K = module.hidden_dim, POOL_ROWS, module.n_class
         self._init_engine(module, device, is_live, _arena_order(list(module.named_parameters())))
         self.Kseg = module.fc_seg.out_features
         self.D = module.input_embed.in_features
         self.pad_idx = module.src_pad_idx
-        self.supcon_weight = 0.0            # --supcon_weight: total loss += weight * SupConLoss over the 'supcon' rows
+        self._supcon_weight = 0.0           # --supcon_weight: total loss += weight * SupConLoss over the 'supcon' rows
         self.supcon_temperature = 0.07      # --temperature
         a, H = self.arena, self.H
         # per layer: [W_ih fwd; W_ih rev] as one [4H, H] operand, [b_ih fwd; b_ih rev] as one [4H] bias
@@ -112,6 +142,24 @@ class RnnEngine(EngineBase):
             self.gw_ih.append(a.grads[ow:ow + 4 * H * H].view(4 * H, H))
             self.b_ih.append(a.params[ob:ob + 4 * H])
             self.gb_ih.append(a.grads[ob:ob + 4 * H])
+
+    @property
+    def supcon_weight(self):
+        return self._supcon_weight
+
+    @supcon_weight.setter
+    def supcon_weight(self, v):
+        check_rnn_shape(self.H, self.Q, wide=self.wide, supcon_weight=v)
+        self._supcon_weight = v
+
+    @property
+    def steps(self):
+        """Whether the LSTM layers run the stepwise kernels (csrc/lstm_steps.hip)."""
+        if self.use_lstm_steps:
+            if not ops.lstm_steps_supported(self.H):
+                raise ValueError(f"hidden {self.H}: the stepwise recurrence does not take it")
+            return True
+        return lstm_route(self.H, self.wide) == "steps"
 
     def _whh(self, l, grad=False):
         f = self.arena.g if grad else self.arena.p
@@ -138,7 +186,8 @@ class RnnEngine(EngineBase):
         inp = w.x
         for l in range(2):
             ops.gemm(GEMM_NT, inp, self.w_ih[l], w.gin, bias=self.b_ih[l], ws=ws)
-            ops.lstm_layer_fwd(w.gin, *self._whh(l), *self._bhh(l), w.y[l], w.gates[l], w.cell[l], w.hprev[l], B, S)
+            lstm_fwd = ops.lstm_steps_layer_fwd if self.steps else ops.lstm_layer_fwd
+            lstm_fwd(w.gin, *self._whh(l), *self._bhh(l), w.y[l], w.gates[l], w.cell[l], w.hprev[l], B, S)
             inp = w.y[l]
         ops.gemm(GEMM_NT, w.y[1], a.p("rnn_fc.weight"), w.tgt, bias=a.p("rnn_fc.bias"), ws=ws)
         ops.avgpool_rows_fwd(w.tgt, w.pooled, B, S, POOL_ROWS)
@@ -201,7 +250,10 @@ class RnnEngine(EngineBase):
         # ---- the two LSTM layers, top down
         h = H // 2
         for l in (1, 0):
-            ops.lstm_layer_bwd(w.d_y[l], *self._whh(l), w.gates[l], w.cell[l], w.dg, B, S)
+            if self.steps:
+                ops.lstm_steps_layer_bwd(w.d_y[l], *self._whh(l), w.gates[l], w.cell[l], w.dg, B, S, w.lstm_ws)
+            else:
+                ops.lstm_layer_bwd(w.d_y[l], *self._whh(l), w.gates[l], w.cell[l], w.dg, B, S)
             inp = w.x if l == 0 else w.y[0]
             wgrad(w.dg, inp, self.gw_ih[l], self.gb_ih[l])                     # dW_ih, d b_ih of both directions
             for d, (gw, gb) in enumerate(zip(self._whh(l, grad=True), self._bhh(l, grad=True))):

@@ -70,6 +70,7 @@ class FUTR(EngineOwner, nn.Module):
         self.transformer = _Transformer(hidden_dim, n_head, num_encoder_layers, num_decoder_layers, hidden_dim * 4)
         self.n_query = n_query
         self.args = args
+        self.r3d_wide_rnn = bool(getattr(args, "wide_rnn", False))         # (opts --wide_rnn: engine_rnn's stepwise route)
         nn.init.xavier_uniform_(self.input_embed.weight)
         self.query_embed = nn.Embedding(self.n_query, hidden_dim)                                          # :31 (unused)
         self.fc_seg = nn.Linear(hidden_dim, n_class - 1)                                                   # :37

@@ -1437,6 +1437,51 @@ def lstm_layer_bwd(dy, whh_fwd, whh_rev, gates, cell, dg, B, S):
                                          _p(dg), _ld(dg), B, S, H, _stream()), "r3d_lstm_layer_bwd")
 
 
+def lstm_steps_supported(H):
+    """Whether the stepwise recurrence (csrc/lstm_steps.hip: one launch per time step) takes hidden H."""
+    return bool(_lib.load().r3d_lstm_steps_supported(H))
+
+
+def lstm_steps_ws_floats(B, H):
+    """Floats of the stepwise backward's workspace: the dc carry [B, H] and the transposed W_hh of both directions."""
+    n = int(_lib.load().r3d_lstm_steps_ws_floats(B, H))
+    if n < 0:
+        raise ValueError(f"r3d_lstm_steps_ws_floats: B {B}, hidden {H} not supported")
+    return n
+
+
+def lstm_steps_layer_fwd(gin, whh_fwd, whh_rev, bhh_fwd, bhh_rev, y, gates, cell, hprev, B, S):
+    """lstm_layer_fwd's arguments and results, by S step launches enqueued from one call."""
+    H = y.shape[1]
+    h = H // 2
+    for t_ in (gin, gates):
+        assert tuple(t_.shape) == (B * S, 8 * h)
+    for t_ in (y, cell, hprev):
+        assert tuple(t_.shape) == (B * S, 2 * h)
+    for w_ in (whh_fwd, whh_rev):
+        assert tuple(w_.shape) == (4 * h, h) and w_.is_contiguous()
+    for b_ in (bhh_fwd, bhh_rev):
+        assert b_.numel() == 4 * h and b_.is_contiguous()
+    check(_lib.load().r3d_lstm_steps_layer_fwd(_p(gin), _ld(gin), _p(whh_fwd), _p(whh_rev), _p(bhh_fwd), _p(bhh_rev), _p(y),
+                                               _ld(y), _p(gates), _ld(gates), _p(cell), _ld(cell), _p(hprev), _ld(hprev), B, S, H,
+                                               _stream()), "r3d_lstm_steps_layer_fwd")
+
+
+def lstm_steps_layer_bwd(dy, whh_fwd, whh_rev, gates, cell, dg, B, S, ws):
+    """lstm_layer_bwd's arguments and result, by S step launches; ws: lstm_steps_ws_floats(B, H) floats."""
+    H = dy.shape[1]
+    h = H // 2
+    for t_ in (gates, dg):
+        assert tuple(t_.shape) == (B * S, 8 * h)
+    assert tuple(cell.shape) == (B * S, 2 * h) and tuple(dy.shape) == (B * S, 2 * h)
+    for w_ in (whh_fwd, whh_rev):
+        assert tuple(w_.shape) == (4 * h, h) and w_.is_contiguous()
+    assert ws.dtype == torch.float32 and ws.is_cuda and ws.is_contiguous() and ws.numel() >= lstm_steps_ws_floats(B, H)
+    check(_lib.load().r3d_lstm_steps_layer_bwd(_p(dy), _ld(dy), _p(whh_fwd), _p(whh_rev), _p(gates), _ld(gates), _p(cell),
+                                               _ld(cell), _p(dg), _ld(dg), B, S, H, _p(ws), _stream()),
+          "r3d_lstm_steps_layer_bwd")
+
+
 # ----------------------------------------------------------------------------------------------------------
 # dilated causal Conv1d with weight normalisation (model/tcn.py; csrc/tconv.hip) and the plain row cross-entropy
 # ----------------------------------------------------------------------------------------------------------

@@ -72,6 +72,10 @@ parser.add_argument("--long_clips", action="store_true", default=False,
                     help="depth-query / label-query models: run the decoder attentions of clips past the attention core's "
                          "limits through the tiled core (head width <= 128; the clip length is then bounded by max_pos_len "
                          "alone).  Shorter clips launch the same kernels either way")
+parser.add_argument("--wide_rnn", action="store_true", default=False,
+                    help="RNN model (model/rnn.py): admit hidden sizes past 256, up to 1024, by running the LSTM recurrence one "
+                         "launch per time step with W_hh spread over the chip (csrc/lstm_steps.hip).  Hidden <= 256 launches "
+                         "the same kernels either way")
 parser.add_argument("--erank_report", action="store_true", default=False,
                     help="after each validate() print the effective rank of the RGB embedding, the depth embedding and the "
                          "fused tokens over every unpadded frame of the validation set (a streaming QR fed by validate()'s "

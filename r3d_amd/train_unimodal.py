@@ -44,12 +44,13 @@ def _unwrap(model):
     return m
 
 
-def _check_shape(core, erank_weight):
+def _check_shape(core, erank_weight, supcon_weight=0.0):
     """The model's own admission rule, on the host, before anything is enqueued."""
     if isinstance(core, FUTRCnn):
         check_cnn_shape(core.hidden_dim, core.n_query, core.n_class, erank_weight, input_dim=core.input_embed.in_features)
     else:
-        check_rnn_shape(core.hidden_dim, core.n_query, erank_weight)
+        check_rnn_shape(core.hidden_dim, core.n_query, erank_weight, wide=getattr(core, "r3d_wide_rnn", False),
+                        supcon_weight=supcon_weight)
 
 
 def _to_dev(data, device):
@@ -117,7 +118,7 @@ def validate(model, val_loader, criterion, pad_idx, device):
 
 def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
     core = _unwrap(model)
-    _check_shape(core, float(getattr(args, "erank_weight", 0.0) or 0.0))
+    _check_shape(core, float(getattr(args, "erank_weight", 0.0) or 0.0), float(getattr(args, "supcon_weight", 0.0) or 0.0))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise NotImplementedError("r3d_amd.train_unimodal trains its model on one GPU; multi-rank torch.distributed "
                                   "runs of it are not supported")
