@@ -20,34 +20,16 @@ from .model.futr_unsupervised_depth import FUTR as FUTRDepthQuery
 from .optim import FlatAdamW
 from .opts import refuse_supcon_weight
 from .parallel import DataParallelStep
+from . import train_common
+from .train_common import (GraphedSteps, adamw_hyper, get_last_non_padding_labels, _graph_key, print_epoch,  # noqa: F401
+                           save_best, unwrap, weighted_accuracy)
 
 
 def _unwrap(model):
-    m = model
-    while hasattr(m, "module") and not isinstance(m, (FUTR, FUTRDepthQuery)):
-        m = m.module
-    if not isinstance(m, (FUTR, FUTRDepthQuery)):
-        raise TypeError("r3d_amd.train_proposed_depth drives r3d_amd.model.futr_safuser_tokenfusion.FUTR (or its "
-                        "BN-blend, activation-magnitude and plain SA-Fuser subclasses) and "
-                        "r3d_amd.model.futr_unsupervised_depth.FUTR")
-    return m
-
-
-def get_last_non_padding_labels(past_label, pad_value):
-    """train_proposed_depth.py:28-50, without the per-clip python loop / host sync."""
-    S = past_label.size(1)
-    pos = torch.arange(S, device=past_label.device).expand_as(past_label)
-    last = torch.where(past_label != pad_value, pos, torch.full_like(pos, -1)).max(dim=1).values
-    out = past_label.gather(1, last.clamp_min(0).unsqueeze(1)).squeeze(1)
-    return torch.where(last >= 0, out, torch.full_like(out, pad_value))
-
-
-def weighted_accuracy(pred, gold, pad_idx, t_n_labels, weight_same=1.0, weight_different=10.0):
-    """train_proposed_depth.py:9-26 (the weight cancels in the ratio; kept for signature parity)."""
-    pred = pred.max(1)[1]
-    mask = gold.ne(pad_idx)
-    total = int(mask.sum())
-    return float((pred.eq(gold) & mask).sum()) / total if total > 0 else 0
+    return unwrap(model, (FUTR, FUTRDepthQuery),
+                  "r3d_amd.train_proposed_depth drives r3d_amd.model.futr_safuser_tokenfusion.FUTR (or its "
+                  "BN-blend, activation-magnitude and plain SA-Fuser subclasses) and "
+                  "r3d_amd.model.futr_unsupervised_depth.FUTR")
 
 
 def _is_m3(core):
@@ -73,67 +55,28 @@ def _to_dev(data, device, gaze=False):
     return out
 
 
-def _graph_key(eng, hyper):
-    """What a captured step depends on besides its batch shape: the AdamW hyper-parameters and the engine's high-water
-    mark of pos_embedding gradient rows (a step clears rows [S, mark) as the mark stood AT CAPTURE, so a longer batch seen
-    since then forces a re-capture)."""
-    return (hyper, eng.pos_grad_rows)
-
-
-class _GraphedSteps:
-    """Replays the fused training step (forward + losses + backward + AdamW + epoch accumulators) as ONE hipGraph per
-    batch shape.  Enqueued launch by launch from Python the 36-launch step is bound by the host (measured 1.68 ms/step
-    against 0.29 ms replayed), so the loop keeps static device buffers per (B, S) shape, copies each batch into them
-    (device-to-device, or straight from the loader when it is given these buffers) and replays.  The first step of a
-    shape runs eagerly (allocations, planner), the second one is captured; lr lives in device memory and may change
-    between replays, the other AdamW hyper-parameters are part of the capture (a change re-captures)."""
+class _GraphedSteps(GraphedSteps):
+    """train_common.GraphedSteps over the fusion models' batch (features, depth_features, past_label, trans_dur_future,
+    trans_future_target and, for the three-modality model, gaze), with the two replicated data-parallel routes."""
 
     def __init__(self, eng, acc_loss, acc_cnt, dp=None, pad_idx=None, rs=None):
         """dp (replicated data parallel): with rs (parallel.RcclStep: RCCL enqueued on the launch stream) the step stays
         ONE graph, exchanges included; otherwise it becomes three graphs around the two torch.distributed all-reduces:
         [forward, losses, backward] -> small bucket (async, under the next graph) -> [depth weight gradient] -> big bucket
         -> [AdamW]."""
-        self.eng, self.acc_loss, self.acc_cnt = eng, acc_loss, acc_cnt
+        super().__init__(eng, acc_loss, acc_cnt)
         self.dp, self.pad_idx, self.rs = dp, pad_idx, rs
-        self.shapes = {}
 
-    def step(self, batch, lr, hyper, training):
-        eng = self.eng
-        key = tuple(tuple(t.shape) for t in batch) + (bool(training), float(eng.erank_weight),
-                                                      str(eng.erank_route), str(eng.erank_fold))
-        st = self.shapes.get(key)
-        if st is None:
-            st = self.shapes[key] = dict(buf=[torch.empty_like(t) for t in batch], seen=0, graph=None, hyper=None)
-        for dst, src in zip(st["buf"], batch):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src, non_blocking=True)
-        eng.set_lr(lr)
+    def _step(self, st, lr, hyper, training):
         if self.dp is not None and self.rs is None:
             return self._step_dp(st, lr, hyper, training)
-        gkey = _graph_key(eng, hyper)
-        if st["graph"] is not None and st["hyper"] == gkey:
-            st["graph"].replay()
-            return
-        eng._drop_ready = None
-        if self.rs is not None:
-            run = lambda: self.rs.run(*st["buf"], self.pad_idx, training, slot=0, lr=lr, hyper=hyper,     # noqa: E731
-                                      after_losses=self._accumulate, stage_den=True, prefill_dropout=False)
-        else:
-            run = lambda: self._enqueue(st["buf"], lr, hyper, training)     # noqa: E731
-        if st["seen"] == 0 or st["hyper"] not in (None, gkey):
-            run()                                                           # eager: sizes every workspace
-            st["seen"], st["hyper"], st["graph"] = 1, gkey, None
-            return
-        g = torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        with torch.cuda.graph(g):
-            run()
-        st["graph"], st["hyper"] = g, gkey
-        g.replay()
+        return super()._step(st, lr, hyper, training)
 
-    def _accumulate(self, loss, counts):
-        self.acc_loss += loss
-        self.acc_cnt += counts
+    def _run(self, st, lr, hyper, training):
+        if self.rs is None:
+            return self._enqueue(st["buf"], lr, hyper, training)
+        self.rs.run(*st["buf"], self.pad_idx, training, slot=0, lr=lr, hyper=hyper, after_losses=self._accumulate,
+                    stage_den=True, prefill_dropout=False)
 
     def _step_dp(self, st, lr, hyper, training):
         eng, dp = self.eng, self.dp
@@ -336,37 +279,12 @@ class _ShardedSteps:
 
 def validate(model, val_loader, criterion, pad_idx, device):
     core = _unwrap(model)
-    model.eval()
-    eng = core.engine()
-    val_loss = 0.0
-    val_class_correct = 0
-    val_class_total = 0
-    val_seg_correct = 0
-    val_seg_total = 0
-    val_weighted_accuracy_total = 0
-    with torch.no_grad():
-        for data in val_loader:
-            if data is None:
-                continue
-            batch = _to_dev(data, eng.device, gaze=_is_m3(core))
-            features, depth_features, past_label, trans_dur_future, trans_future_target = batch[:5]
-            kw = dict(gaze=batch[5]) if len(batch) == 6 else {}
-            out = eng.forward(features, depth_features, past_label, "val", training=False, need_grad=False, **kw)
-            loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, with_grad=False, val_mode=True)
-            lv, cv = loss.cpu(), counts.cpu()                       # one readback per validation clip
-            val_loss += float(lv[1] + lv[2])                        # action CE + duration (:86,100)
-            val_class_correct += int(cv[2])
-            val_class_total += int(cv[3])
-            val_weighted_accuracy_total += weighted_accuracy(
-                out["action"].reshape(-1, out["action"].size(-1)), trans_future_target.view(-1), pad_idx,
-                get_last_non_padding_labels(past_label, pad_idx))
-    val_loss /= len(val_loader)
-    val_accuracy = val_class_correct / val_class_total if val_class_total else 0
-    val_seg_accuracy = val_seg_correct / val_seg_total if val_seg_total else 0
-    val_weighted_accuracy = val_weighted_accuracy_total / len(val_loader)
-    print(f"Validation Loss: {val_loss:.3f}, Class Accuracy: {val_accuracy:.3f}, Segmentation Accuracy: "
-          f"{val_seg_accuracy:.3f}, Weighted Accuracy: {val_weighted_accuracy:.3f}")
-    return val_loss, val_accuracy, val_weighted_accuracy
+    gaze = _is_m3(core)
+
+    def forward(eng, batch):
+        kw = dict(gaze=batch[5]) if gaze else {}
+        return (eng.forward(*batch[:3], "val", training=False, need_grad=False, **kw),) + batch[2:5]
+    return train_common.validate(model, core, val_loader, pad_idx, lambda data, dev: _to_dev(data, dev, gaze=gaze), forward)
 
 
 def _print_erank(eng):
@@ -382,19 +300,17 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     refuse_supcon_weight(args, "train_proposed_depth")
     core = _unwrap(model)
     m3 = _is_m3(core)
+    parallel = bool(dist.is_available() and dist.is_initialized() and
+                    (dist.get_world_size() > 1 or os.environ.get("R3D_REHEARSE_DIST") == "1"))
     if m3:          # (before anything is moved or allocated: what the three-modality engine does not run)
         from .engine_m3 import check_m3_args
-        check_m3_args(pixel_shard=bool(getattr(args, "pixel_shard", False)),
-                      parallel=bool(dist.is_available() and dist.is_initialized() and
-                                    (dist.get_world_size() > 1 or os.environ.get("R3D_REHEARSE_DIST") == "1")))
+        check_m3_args(pixel_shard=bool(getattr(args, "pixel_shard", False)), parallel=parallel)
     model.to(device)
     model.train()
     eng = core.engine()
     eng.defer_tail = True       # every step here is forward -> losses -> backward: tail forward, losses and tail backward
                                 # run as one launch (validate()'s forwards carry no gradient workspace and are unaffected)
     dp = None
-    parallel = dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1
-                                                                  or os.environ.get("R3D_REHEARSE_DIST") == "1")
     if getattr(args, "erank_route", "jacobi") == "tall" and parallel:
         raise ValueError("--erank_route tall under data parallelism: the tall rank route runs on one GPU")
     if getattr(args, "erank_report", False) and parallel:
@@ -418,7 +334,6 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     if eng.rank_penalty:                 # (the engines without a fused token matrix refuse the penalty itself)
         eng.erank_route = str(getattr(args, "erank_route", "jacobi"))
     print("Training Start")
-    best_val_loss = float("inf")
     best_val_acc = 0
     best_weight_acc = 0
     acc_loss = torch.zeros(4, dtype=torch.float64, device=eng.device)
@@ -471,8 +386,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
                 prep = lambda d: (d[0].float().contiguous(), d[1].float().contiguous(), d[2].long().contiguous(),     # noqa: E731
                                   d[3].float().contiguous(), d[4].long().contiguous())
                 sharded.step(prep(cur[1]), (epoch, cur[0]), prep(nxt[1]) if nxt is not None else None,
-                             (epoch, nxt[0]) if nxt is not None else None, g["lr"],
-                             (g["weight_decay"], tuple(g["betas"]), g["eps"]), model.training)
+                             (epoch, nxt[0]) if nxt is not None else None, g["lr"], adamw_hyper(g), model.training)
                 n_steps += 1
                 last_i = cur[0]
                 cur = nxt
@@ -490,7 +404,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
             if graphed is not None and isinstance(optimizer, FlatAdamW):
                 graphed.step([features.contiguous(), depth_features.contiguous(), past_label.contiguous(),
                               trans_dur_future.contiguous(), trans_future_target.contiguous()] + list(batch[5:]), g["lr"],
-                             (g["weight_decay"], tuple(g["betas"]), g["eps"]), model.training)
+                             adamw_hyper(g), model.training)
                 n_steps += 1
                 if erank_every and n_steps % erank_every == 0:
                     _print_erank(eng)
@@ -521,15 +435,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
             n_steps += 1
             if erank_every and n_steps % erank_every == 0:
                 _print_erank(eng)
-        lsum, csum = acc_loss.cpu(), acc_cnt.cpu()                  # the single device->host read of the epoch
-        denom = i + 1                                                # the reference divides by (i+1), skipped or not (:218)
-        epoch_loss = float(lsum[3]) / denom if denom else 0.0
-        print("Epoch [", (epoch + 1), "/", args.epochs, "] Loss : %.3f" % epoch_loss)
-        if args.anticipate:
-            accuracy = int(csum[2]) / int(csum[3]) if int(csum[3]) else 0.0
-            print("Training Acc :%.3f" % accuracy, "CE loss :%.3f" % (float(lsum[1]) / denom if denom else 0.0))
-            if args.task == "long":
-                print("dur loss: %.5f" % (float(lsum[2]) / denom if denom else 0.0))
+        print_epoch(args, epoch, i, acc_loss, acc_cnt)               # (the (i+1) denominator: :218)
         scheduler.step()
         if dp is not None and dp.tp is not None:
             dp.tp.sync_full_weight()                                 # validation and checkpoints see the complete weight
@@ -546,14 +452,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         if getattr(args, "restore_train_mode", False):
             model.train()
         if (val_acc > best_val_acc or weight_acc > best_weight_acc) and is_main:
-            best_val_loss, best_val_acc, best_weight_acc = val_loss, val_acc, weight_acc
-            save_path = os.path.join(model_save_path)
-            save_file = os.path.join(save_path, "seed_" + str(seed) + "_checkpoint" + str(epoch) + ".ckpt")
-            torch.save(model.state_dict(), save_file)
-            best_save_file = os.path.join(save_path, "seed_" + str(seed) + "_best.ckpt")
-            if os.path.exists(best_save_file):
-                os.remove(best_save_file)
-            torch.save(model.state_dict(), best_save_file)
-            print(f"Best model saved with validation loss: {best_val_loss:.3f}")
+            best_val_acc, best_weight_acc = val_acc, weight_acc
+            save_best(model, model_save_path, seed, epoch, val_loss)
     eng.defer_tail = False
     return model

@@ -22,16 +22,11 @@ import torch
 from .model.tcn import MustafaNet1DTCN
 from .optim import FlatAdamW
 from .opts import refuse_supcon_weight
-from .train_proposed_depth import _GraphedSteps
+from .train_common import GraphedSteps, adamw_hyper, unwrap
 
 
 def _unwrap(model):
-    m = model
-    while hasattr(m, "module") and not isinstance(m, MustafaNet1DTCN):
-        m = m.module
-    if not isinstance(m, MustafaNet1DTCN):
-        raise TypeError("r3d_amd.train_tcn drives r3d_amd.model.tcn.MustafaNet1DTCN")
-    return m
+    return unwrap(model, MustafaNet1DTCN, "r3d_amd.train_tcn drives r3d_amd.model.tcn.MustafaNet1DTCN")
 
 
 def _to_dev(data, device):
@@ -39,8 +34,12 @@ def _to_dev(data, device):
     return (features.to(device=device, dtype=torch.float32).contiguous(), trans_future_target.to(device).long().contiguous())
 
 
-class _TcnSteps(_GraphedSteps):
-    """_GraphedSteps over the pair (features, trans_future_target)."""
+class _TcnSteps(GraphedSteps):
+    """GraphedSteps over the pair (features, trans_future_target)."""
+
+    def __init__(self, eng, acc_loss, acc_cnt, pad_idx=None, graph=True):
+        super().__init__(eng, acc_loss, acc_cnt, graph)
+        self.pad_idx = pad_idx
 
     def _enqueue(self, buf, lr, hyper, training):
         feats, tgt = buf
@@ -90,7 +89,7 @@ def train(args, model, train_loader, val_loader, optimizer, scheduler, criterion
     acc_loss = torch.zeros(4, dtype=torch.float64, device=eng.device)
     acc_cnt = torch.zeros(4, dtype=torch.int64, device=eng.device)
     fused_opt = isinstance(optimizer, FlatAdamW) or type(optimizer) is torch.optim.AdamW
-    graphed = _TcnSteps(eng, acc_loss, acc_cnt, pad_idx=pad_idx) if getattr(args, "graph_steps", True) else None
+    steps = _TcnSteps(eng, acc_loss, acc_cnt, pad_idx=pad_idx, graph=getattr(args, "graph_steps", True))
     for epoch in range(args.epochs):
         acc_loss.zero_()
         acc_cnt.zero_()
@@ -99,14 +98,7 @@ def train(args, model, train_loader, val_loader, optimizer, scheduler, criterion
             features, target = _to_dev(data, eng.device)
             g = optimizer.param_groups[0]
             if fused_opt and len(optimizer.param_groups) == 1 and not g.get("amsgrad", False) and not g.get("maximize", False):
-                hyper = (g["weight_decay"], tuple(g["betas"]), g["eps"])
-                if graphed is not None:
-                    graphed.step([features, target], g["lr"], hyper, model.training)
-                else:
-                    loss, counts = eng.train_step(features, target, pad_idx, g["lr"], hyper[0], training=model.training,
-                                                  betas=hyper[1], eps=hyper[2])
-                    acc_loss += loss
-                    acc_cnt += counts
+                steps.step([features, target], g["lr"], adamw_hyper(g), model.training)
                 continue
             optimizer.zero_grad()                                   # any other optimiser: expose the arena gradients to it
             eng.forward(features, training=model.training)

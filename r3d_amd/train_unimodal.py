@@ -3,7 +3,7 @@
 and ``validate(model, val_loader, criterion, pad_idx, device)`` with the reference's signatures, skip rules, loss
 composition, prints and checkpoint names, driving either unimodal baseline (r3d_amd.model.rnn.FUTR or
 r3d_amd.model.cnn.FUTR; the shape check dispatches on the model, everything else is shared).  Each batch is one replay of
-the fused step (forward + 3 losses + backward + AdamW, train_proposed_depth._GraphedSteps) with no device->host sync;
+the fused step (forward + 3 losses + backward + AdamW, train_common.GraphedSteps) with no device->host sync;
 epoch statistics are read back once per epoch.
 
 It is train_proposed_depth's loop except where the reference's differs (each can be checked against the cited line):
@@ -22,8 +22,6 @@ labels ``past_label.view(-1)`` -- the use main_nturgbd.py:137 prepares and the r
 to the step's loss, inside the step (the engine's losses / backward; the CNN model's rows are x, hidden <= 256); the epoch's ``Loss`` includes it and one
 ``supcon loss`` line follows the ``seg loss`` line.  validate() is unchanged.
 """
-import os
-
 import torch
 import torch.distributed as dist
 
@@ -32,16 +30,13 @@ from .model.cnn import FUTR as FUTRCnn
 from .optim import FlatAdamW
 from .engine_rnn import check_rnn_shape
 from .engine_cnn import check_cnn_shape
-from .train_proposed_depth import _GraphedSteps, get_last_non_padding_labels, weighted_accuracy  # noqa: F401
+from . import train_common
+from .train_common import (GraphedSteps, adamw_hyper, get_last_non_padding_labels, print_epoch, save_best,  # noqa: F401
+                           unwrap, weighted_accuracy)
 
 
 def _unwrap(model):
-    m = model
-    while hasattr(m, "module") and not isinstance(m, (FUTR, FUTRCnn)):
-        m = m.module
-    if not isinstance(m, (FUTR, FUTRCnn)):
-        raise TypeError("r3d_amd.train_unimodal drives r3d_amd.model.rnn.FUTR or r3d_amd.model.cnn.FUTR")
-    return m
+    return unwrap(model, (FUTR, FUTRCnn), "r3d_amd.train_unimodal drives r3d_amd.model.rnn.FUTR or r3d_amd.model.cnn.FUTR")
 
 
 def _check_shape(core, erank_weight, supcon_weight=0.0):
@@ -61,12 +56,12 @@ def _to_dev(data, device):
             trans_future_target.to(device).long().contiguous())
 
 
-class _UnimodalSteps(_GraphedSteps):
-    """_GraphedSteps over the 4-tuple (features, past_label, trans_dur_future, trans_future_target): no depth buffer.
+class _UnimodalSteps(GraphedSteps):
+    """GraphedSteps over the 4-tuple (features, past_label, trans_dur_future, trans_future_target): no depth buffer.
     acc_sc: the epoch's sum of the supervised contrastive loss (--supcon_weight > 0), accumulated inside the step."""
 
-    def __init__(self, eng, acc_loss, acc_cnt, acc_sc=None):
-        super().__init__(eng, acc_loss, acc_cnt)
+    def __init__(self, eng, acc_loss, acc_cnt, acc_sc=None, graph=True):
+        super().__init__(eng, acc_loss, acc_cnt, graph)
         self.acc_sc = acc_sc
 
     def _enqueue(self, buf, lr, hyper, training):
@@ -84,36 +79,9 @@ class _UnimodalSteps(_GraphedSteps):
 
 
 def validate(model, val_loader, criterion, pad_idx, device):
-    core = _unwrap(model)
-    model.eval()
-    eng = core.engine()
-    val_loss = 0.0
-    val_class_correct = 0
-    val_class_total = 0
-    val_seg_correct = 0
-    val_seg_total = 0
-    val_weighted_accuracy_total = 0
-    with torch.no_grad():
-        for data in val_loader:
-            if data is None:
-                continue
-            features, past_label, trans_dur_future, trans_future_target = _to_dev(data, eng.device)
-            out = eng.forward(features, None, past_label, "train", training=False, need_grad=False)     # (:91)
-            loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, with_grad=False, val_mode=True)
-            lv, cv = loss.cpu(), counts.cpu()                       # one readback per validation clip
-            val_loss += float(lv[1] + lv[2])                        # action CE + duration (:104,112)
-            val_class_correct += int(cv[2])
-            val_class_total += int(cv[3])
-            val_weighted_accuracy_total += weighted_accuracy(
-                out["action"].reshape(-1, out["action"].size(-1)), trans_future_target.view(-1), pad_idx,
-                get_last_non_padding_labels(past_label, pad_idx))
-    val_loss /= len(val_loader)
-    val_accuracy = val_class_correct / val_class_total if val_class_total else 0
-    val_seg_accuracy = val_seg_correct / val_seg_total if val_seg_total else 0
-    val_weighted_accuracy = val_weighted_accuracy_total / len(val_loader)
-    print(f"Validation Loss: {val_loss:.3f}, Class Accuracy: {val_accuracy:.3f}, Segmentation Accuracy: "
-          f"{val_seg_accuracy:.3f}, Weighted Accuracy: {val_weighted_accuracy:.3f}")
-    return val_loss, val_accuracy, val_weighted_accuracy
+    def forward(eng, batch):                                                                             # (:91)
+        return (eng.forward(batch[0], None, batch[1], "train", training=False, need_grad=False),) + batch[1:]
+    return train_common.validate(model, _unwrap(model), val_loader, pad_idx, _to_dev, forward)
 
 
 def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
@@ -130,13 +98,12 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     eng.supcon_temperature = float(getattr(args, "temperature", 0.07))
     min_batch = getattr(args, "min_batch", 8)
     print("Training Start")
-    best_val_loss = float("inf")
     best_val_acc = 0
     best_weight_acc = 0
     acc_loss = torch.zeros(4, dtype=torch.float64, device=eng.device)
     acc_cnt = torch.zeros(4, dtype=torch.int64, device=eng.device)
     acc_sc = torch.zeros(1, dtype=torch.float64, device=eng.device)
-    graphed = _UnimodalSteps(eng, acc_loss, acc_cnt, acc_sc) if getattr(args, "graph_steps", True) else None
+    steps = _UnimodalSteps(eng, acc_loss, acc_cnt, acc_sc, graph=getattr(args, "graph_steps", True))
     for epoch in range(args.epochs):
         acc_loss.zero_()
         acc_cnt.zero_()
@@ -149,49 +116,24 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
                 continue
             features, past_label, trans_dur_future, trans_future_target = _to_dev(data, eng.device)
             g = optimizer.param_groups[0]
-            if graphed is not None and isinstance(optimizer, FlatAdamW):
-                graphed.step([features, past_label, trans_dur_future, trans_future_target], g["lr"],
-                             (g["weight_decay"], tuple(g["betas"]), g["eps"]), model.training)
+            if isinstance(optimizer, FlatAdamW):
+                steps.step([features, past_label, trans_dur_future, trans_future_target], g["lr"], adamw_hyper(g),
+                           model.training)
                 continue
-            eng.forward(features, None, past_label, "train", training=model.training)
-            fused_opt = isinstance(optimizer, FlatAdamW)
-            loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future, tick=fused_opt)
+            eng.forward(features, None, past_label, "train", training=model.training)    # any other torch optimiser:
+            loss, counts = eng.losses(past_label, trans_future_target, trans_dur_future)
             eng.backward()
-            if fused_opt:
-                eng.adamw(g["lr"], g["weight_decay"], betas=g["betas"], eps=g["eps"], ticked=True)
-            else:                                   # any other torch optimiser: expose the arena gradients to it
-                eng.arena.attach_grads(core.named_parameters())
-                optimizer.step()
+            eng.arena.attach_grads(core.named_parameters())                              # expose the arena gradients to it
+            optimizer.step()
             acc_loss += loss
             acc_cnt += counts
             if eng.supcon_weight:
                 acc_sc += eng.last["w"].sc_loss
-        # the single device->host read of the epoch
-        lsum, csum = (torch.cat([acc_loss, acc_sc]) if eng.supcon_weight else acc_loss).cpu(), acc_cnt.cpu()
-        denom = i + 1                                                # the reference divides by (i+1), skipped or not
-        epoch_loss = float(lsum[3]) / denom if denom else 0.0
-        print("Epoch [", (epoch + 1), "/", args.epochs, "] Loss : %.3f" % epoch_loss)
-        if args.anticipate:
-            accuracy = int(csum[2]) / int(csum[3]) if int(csum[3]) else 0.0
-            print("Training Acc :%.3f" % accuracy, "CE loss :%.3f" % (float(lsum[1]) / denom if denom else 0.0))
-            if args.task == "long":
-                print("dur loss: %.5f" % (float(lsum[2]) / denom if denom else 0.0))
-        if args.seg:
-            acc_seg = int(csum[0]) / int(csum[1]) if int(csum[1]) else 0.0
-            print("seg loss :%.3f" % (float(lsum[0]) / denom if denom else 0.0), ", seg acc : %.5f" % acc_seg)
-        if eng.supcon_weight:
-            print("supcon loss :%.3f" % (float(lsum[4]) / denom if denom else 0.0))
+        print_epoch(args, epoch, i, acc_loss, acc_cnt, acc_sc if eng.supcon_weight else None, seg_line=args.seg)
         scheduler.step()
         val_loss, val_acc, weight_acc = validate(model, val_loader, criterion, pad_idx, device)
         if val_acc > best_val_acc or weight_acc > best_weight_acc:
-            best_val_loss, best_val_acc, best_weight_acc = val_loss, val_acc, weight_acc
-            save_path = os.path.join(model_save_path)
-            save_file = os.path.join(save_path, "seed_" + str(seed) + "_checkpoint" + str(epoch) + ".ckpt")
-            torch.save(model.state_dict(), save_file)
-            best_save_file = os.path.join(save_path, "seed_" + str(seed) + "_best.ckpt")
-            if os.path.exists(best_save_file):
-                os.remove(best_save_file)
-            torch.save(model.state_dict(), best_save_file)
-            print(f"Best model saved with validation loss: {best_val_loss:.3f}")
+            best_val_acc, best_weight_acc = val_acc, weight_acc
+            save_best(model, model_save_path, seed, epoch, val_loss)
         model.train()
     return model

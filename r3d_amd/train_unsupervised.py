@@ -17,8 +17,6 @@ adds the UNWEIGHTED cal_loss action loss and no duration loss (:179,193-196); va
 train() never switches back, so dropout is off from the second epoch on; the checkpoint rule and file names (:413-425).
 The reference raises a NameError with args.seg or args.anticipate off (:357,362 read l2_correct / loss / loss_dur
 unconditionally): both are refused here with a ValueError that says so."""
-import os
-
 import torch
 import torch.distributed as dist
 
@@ -26,6 +24,7 @@ from .engine_l3 import VAL_L3_PAD
 from .loss.temporal import get_cluster_intervals  # noqa: F401
 from .model.futr_unsupervised_temp3 import FUTR
 from .optim import FlatAdamW
+from .train_common import save_best, unwrap
 from . import ops
 
 
@@ -58,12 +57,7 @@ def weighted_accuracy(pred, gold, pad_idx, t_n_labels, weight_same=1.0, weight_d
 
 
 def _unwrap(model):
-    m = model
-    while hasattr(m, "module") and not isinstance(m, FUTR):
-        m = m.module
-    if not isinstance(m, FUTR):
-        raise TypeError("r3d_amd.train_unsupervised drives r3d_amd.model.futr_unsupervised_temp3.FUTR")
-    return m
+    return unwrap(model, FUTR, "r3d_amd.train_unsupervised drives r3d_amd.model.futr_unsupervised_temp3.FUTR")
 
 
 def _to_dev(data, device):
@@ -141,7 +135,6 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     model.train()
     eng = core.engine()
     print("Training Start")
-    best_val_loss = float("inf")
     best_val_acc = 0
     best_weight_acc = 0
     acc = (torch.zeros(6, dtype=torch.float64, device=eng.device), torch.zeros(6, dtype=torch.int64, device=eng.device))
@@ -187,13 +180,6 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
         scheduler.step()
         val_loss, val_acc, weight_acc = validate(model, val_loader, criterion, pad_idx, device)
         if val_acc > best_val_acc or weight_acc > best_weight_acc:
-            best_val_loss, best_val_acc, best_weight_acc = val_loss, val_acc, weight_acc
-            save_path = os.path.join(model_save_path)
-            save_file = os.path.join(save_path, "seed_" + str(seed) + "_checkpoint" + str(epoch) + ".ckpt")
-            torch.save(model.state_dict(), save_file)
-            best_save_file = os.path.join(save_path, "seed_" + str(seed) + "_best.ckpt")
-            if os.path.exists(best_save_file):
-                os.remove(best_save_file)
-            torch.save(model.state_dict(), best_save_file)
-            print(f"Best model saved with validation loss: {best_val_loss:.3f}")
+            best_val_acc, best_weight_acc = val_acc, weight_acc
+            save_best(model, model_save_path, seed, epoch, val_loss)
     return model
