@@ -4,7 +4,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import GemmDesc, GEMM_NT, GEMM_NN, GEMM_TN, check
 
 
@@ -32,6 +32,11 @@ def _ld(t):
     """leading dimension of a 2-D row-major (possibly column-sliced) tensor"""
     assert t.dim() == 2 and t.stride(1) == 1, "expected a 2-D tensor with unit column stride"
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _ld0(t):
+    """_ld of an optional operand: 0 when it is absent"""
+    return 0 if t is None else _ld(t)
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -235,7 +240,7 @@ class RowsumGroup:
             rows, cols = s1.shape
             assert tuple(dst.shape) == (mod, cols) and (s2 is None or s2.shape == s1.shape)
             arr[i].src1, arr[i].src2, arr[i].dst = s1.data_ptr(), (s2.data_ptr() if s2 is not None else None), dst.data_ptr()
-            arr[i].ld1, arr[i].ld2, arr[i].ldd = _ld(s1), (_ld(s2) if s2 is not None else 0), _ld(dst)
+            arr[i].ld1, arr[i].ld2, arr[i].ldd = _ld(s1), _ld0(s2), _ld(dst)
             arr[i].rows, arr[i].cols, arr[i].mod = rows, cols, mod
         self.jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(jobs[0][0].device)
         self.n = n
@@ -298,11 +303,9 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, *, pair_in=
         wsb = partial
     else:
         wsb = ws.get(need) if (need > 0 and dgamma is not None) else None
-    check(lib.r3d_layernorm_bwd(_p(dy), _ld(dy), 1 if pair_in else 0, _p(dy2), _ld(dy2) if dy2 is not None else 0, _p(x), _ld(x), _p(mean), _p(rstd), _p(gamma), _p(beta),
-                                1 if relu else 0, _p(add1), _ld(add1) if add1 is not None else 0, _p(add2),
-                                _ld(add2) if add2 is not None else 0, _p(dx), _ld(dx), _p(dx2),
-                                _ld(dx2) if dx2 is not None else 0, _p(drop_mask),
-                                _ld(drop_mask) if drop_mask is not None else 0, drop_scale, _p(dgamma), _p(dbeta),
+    check(lib.r3d_layernorm_bwd(_p(dy), _ld(dy), 1 if pair_in else 0, _p(dy2), _ld0(dy2), _p(x), _ld(x), _p(mean), _p(rstd),
+                                _p(gamma), _p(beta), 1 if relu else 0, _p(add1), _ld0(add1), _p(add2), _ld0(add2), _p(dx),
+                                _ld(dx), _p(dx2), _ld0(dx2), _p(drop_mask), _ld0(drop_mask), drop_scale, _p(dgamma), _p(dbeta),
                                 _p(wsb), rows, H, 1 if partial is not None else 0, _stream()), "r3d_layernorm_bwd")
 
 
@@ -348,10 +351,10 @@ def gemm_ln_fwd(jobs, mha=None):
             assert j["w"].shape == (H, t.shape[1]) and t.shape[0] == M
             a.A, a.lda, a.W, a.ldw, a.K = t.data_ptr(), _ld(t), j["w"].data_ptr(), _ld(j["w"]), t.shape[1]
             a.bias = _pv(g("bias"))
-            a.drop_mask, a.lddrop = _pv(g("drop_mask")), _ld(g("drop_mask")) if g("drop_mask") is not None else 0
+            a.drop_mask, a.lddrop = _pv(g("drop_mask")), _ld0(g("drop_mask"))
             a.drop_scale = g("drop_scale") or 1.0
-            a.res1, a.ldr1 = _pv(g("res1")), _ld(g("res1")) if g("res1") is not None else 0
-            a.res2, a.ldr2 = _pv(g("res2")), _ld(g("res2")) if g("res2") is not None else 0
+            a.res1, a.ldr1 = _pv(g("res1")), _ld0(g("res1"))
+            a.res2, a.ldr2 = _pv(g("res2")), _ld0(g("res2"))
         else:
             a.K = 0
         a.pre_out, a.ldpre = j["pre"].data_ptr(), _ld(j["pre"])
@@ -418,62 +421,61 @@ class WeightPlanes:
         return self._view[key]
 
 
-class FuserChainFwd:
-    """The argument block of r3d_fuser_chain_fwd (csrc/fuser_chain.hip), built once per workspace: every operand is a
-    dense row-major tensor whose address is fixed for the life of the workspace (the dropout masks are optional)."""
+_TORCH_DTYPE = {"uint8_t": torch.uint8, "int64_t": torch.int64, "float": torch.float32}
+
+
+def chain_operands(struct):
+    """-> (operands {name: torch dtype}, plane names) of a chain's argument struct, read from the header's pointer fields in
+    their order: the planes are the pl_* pointers, the operands every other pointer but the profiling aid `timeline`, each
+    with the dtype of its pointee."""
+    ptrs = {n: _abi.pointee(t) for n, t in struct.C_TYPES.items() if t.endswith("*") and n != "timeline"}
+    return ({n: _TORCH_DTYPE[p] for n, p in ptrs.items() if not n.startswith("pl_")},
+            [n for n in ptrs if n.startswith("pl_")])
+
+
+class _ChainArgs:
+    """The argument block of one chain launch, built once per workspace: every operand is a dense row-major tensor whose
+    address is fixed for the life of the workspace.  A subclass states its STRUCT, the names of its sizes (DIMS) and the
+    operands that may be absent (OPTIONAL); `planes` is a dict name -> device address of a weight's bf16x3 planes, or None."""
 
     def __init__(self, **t):
-        from ._lib import FuserChainFwdArgs
-        a = FuserChainFwdArgs()
-        dims = {k: t.pop(k) for k in ("N", "S", "K", "H", "add_xres", "B", "Q", "heads")}
+        a = self.STRUCT()
+        operands, plane_names = chain_operands(self.STRUCT)
+        dims = {k: t.pop(k) for k in self.DIMS}
         a.drop_scale = float(t.pop("drop_scale", 1.0))
-        opt = {"y", "drop_sa", "drop_d1"}
-        planes = t.pop("planes", None)                 # dict name -> device address of the weight's bf16x3 planes, or None
+        planes = t.pop("planes", None)
         if planes is not None:
-            for name in FuserChainFwdArgs._PLANES:
+            for name in plane_names:
                 setattr(a, name, planes[name])
-        for name in FuserChainFwdArgs._PTRS + FuserChainFwdArgs._PTRS2:
+        for name, dtype in operands.items():
             v = t.pop(name, None)
             if v is None:
-                assert name in opt, name
+                assert name in self.OPTIONAL, name
                 continue
             assert v.is_cuda and v.is_contiguous(), name
-            assert v.dtype == (torch.uint8 if name.startswith("drop_") else torch.float32), name
+            assert v.dtype == dtype, name
             setattr(a, name, v.data_ptr())
         assert not t, t.keys()
         for k, v in dims.items():
             setattr(a, k, int(v))
         self.args = a
+
+
+class FuserChainFwd(_ChainArgs):
+    """The argument block of r3d_fuser_chain_fwd (csrc/fuser_chain.hip); the dropout masks are optional."""
+    STRUCT = _lib.FuserChainFwdArgs
+    DIMS = ("N", "S", "K", "H", "add_xres", "B", "Q", "heads")
+    OPTIONAL = {"y", "drop_sa", "drop_d1"}
 
     def launch(self):
         check(_lib.load().r3d_fuser_chain_fwd(C.byref(self.args), _stream()), "r3d_fuser_chain_fwd")
 
 
-class FuserChainBwd:
-    """The argument block of r3d_fuser_chain_bwd, built once per workspace (see FuserChainFwd)."""
-
-    def __init__(self, **t):
-        from ._lib import FuserChainBwdArgs
-        a = FuserChainBwdArgs()
-        dims = {k: t.pop(k) for k in ("N", "S", "K", "H", "add_xres", "B", "Q", "heads")}
-        a.drop_scale = float(t.pop("drop_scale", 1.0))
-        opt = {"d_extra", "drop_x0", "drop_d1", "drop_sa", "d_h2", "d_h1", "t1pre_out"}
-        planes = t.pop("planes", None)
-        if planes is not None:
-            for name in FuserChainBwdArgs._PLANES:
-                setattr(a, name, planes[name])
-        for name in FuserChainBwdArgs._PTRS:
-            v = t.pop(name, None)
-            if v is None:
-                assert name in opt, name
-                continue
-            assert v.is_cuda and v.is_contiguous(), name
-            assert v.dtype == (torch.uint8 if name.startswith("drop_") else torch.float32), name
-            setattr(a, name, v.data_ptr())
-        assert not t, t.keys()
-        for k, v in dims.items():
-            setattr(a, k, int(v))
-        self.args = a
+class FuserChainBwd(_ChainArgs):
+    """The argument block of r3d_fuser_chain_bwd (see FuserChainFwd)."""
+    STRUCT = _lib.FuserChainBwdArgs
+    DIMS = FuserChainFwd.DIMS
+    OPTIONAL = {"d_extra", "drop_x0", "drop_d1", "drop_sa", "d_h2", "d_h1", "t1pre_out"}
 
     def launch(self):
         check(_lib.load().r3d_fuser_chain_bwd(C.byref(self.args), _stream()), "r3d_fuser_chain_bwd")
@@ -483,34 +485,13 @@ def decoder_chain_supported(H, Q, heads, S):
     return bool(_lib.load().r3d_decoder_chain_supported(H, Q, heads, S))
 
 
-class DecoderChain:
-    """The argument block of r3d_decoder_chain (csrc/decoder_chain.hip), built once per workspace; key_label is re-pointed
-    per call (the step's label tensor)."""
-
-    def __init__(self, **t):
-        from ._lib import DecoderChainArgs
-        a = DecoderChainArgs()
-        dims = {k: t.pop(k) for k in ("pad_idx", "B", "S", "H", "Q", "heads")}
-        a.drop_scale = float(t.pop("drop_scale", 1.0))
-        opt = {"key_label", "drop_ca", "drop_d2", "drop_ff", "drop_d3", "d_t3pre", "d_ff2", "d_ff1", "d_t2pre", "d_cap", "d_cao",
-               "d_caq", "d_cakv", "part_d2"}
-        planes = t.pop("planes", None)
-        if planes is not None:
-            for name in ("pl_wo", "pl_w1", "pl_w2", "pl_w2_t", "pl_w1_t", "pl_wo_t"):
-                setattr(a, name, planes[name])
-        for name in DecoderChainArgs._PTRS:
-            v = t.pop(name, None)
-            if v is None:
-                assert name in opt, name
-                continue
-            assert v.is_cuda and v.is_contiguous(), name
-            want = torch.uint8 if name.startswith("drop_") else (torch.int64 if name == "key_label" else torch.float32)
-            assert v.dtype == want, name
-            setattr(a, name, v.data_ptr())
-        assert not t, t.keys()
-        for k, v in dims.items():
-            setattr(a, k, int(v))
-        self.args = a
+class DecoderChain(_ChainArgs):
+    """The argument block of r3d_decoder_chain (csrc/decoder_chain.hip); key_label is re-pointed per call (the step's label
+    tensor)."""
+    STRUCT = _lib.DecoderChainArgs
+    DIMS = ("pad_idx", "B", "S", "H", "Q", "heads")
+    OPTIONAL = {"key_label", "drop_ca", "drop_d2", "drop_ff", "drop_d3", "d_t3pre", "d_ff2", "d_ff1", "d_t2pre", "d_cap", "d_cao",
+                "d_caq", "d_cakv", "part_d2"}
 
     def launch(self, phases, key_label=None, tail=None, ws=None):
         """tail: a filled TailLossesArgs (phases & 2), ws: the loss scratch."""
@@ -533,14 +514,14 @@ def layernorm_bwd_multi(jobs, mha=None):
         a = arr[i]
         g = lambda k: j.get(k)                    # noqa: E731
         a.dy, a.lddy, a.pair_in = j["dy"].data_ptr(), _ld(j["dy"]), 1 if g("pair_in") else 0
-        a.dy2, a.lddy2 = _pv(g("dy2")), _ld(g("dy2")) if g("dy2") is not None else 0
+        a.dy2, a.lddy2 = _pv(g("dy2")), _ld0(g("dy2"))
         a.x, a.ldx, a.mean, a.rstd = j["x"].data_ptr(), _ld(j["x"]), j["mean"].data_ptr(), j["rstd"].data_ptr()
         a.gamma, a.beta, a.relu = j["gamma"].data_ptr(), j["beta"].data_ptr(), 1 if g("relu") else 0
-        a.add1, a.ldadd1 = _pv(g("add1")), _ld(g("add1")) if g("add1") is not None else 0
-        a.add2, a.ldadd2 = _pv(g("add2")), _ld(g("add2")) if g("add2") is not None else 0
+        a.add1, a.ldadd1 = _pv(g("add1")), _ld0(g("add1"))
+        a.add2, a.ldadd2 = _pv(g("add2")), _ld0(g("add2"))
         a.dx, a.lddx = j["dx"].data_ptr(), _ld(j["dx"])
-        a.dx2, a.lddx2 = _pv(g("dx2")), _ld(g("dx2")) if g("dx2") is not None else 0
-        a.drop_mask, a.lddrop = _pv(g("drop_mask")), _ld(g("drop_mask")) if g("drop_mask") is not None else 0
+        a.dx2, a.lddx2 = _pv(g("dx2")), _ld0(g("dx2"))
+        a.drop_mask, a.lddrop = _pv(g("drop_mask")), _ld0(g("drop_mask"))
         a.drop_scale = g("drop_scale") or 1.0
         a.dgamma, a.dbeta, a.ws = j["dgamma"].data_ptr(), j["dbeta"].data_ptr(), j["partial"].data_ptr()
         a.rows, a.H = rows, H
@@ -574,7 +555,7 @@ def layernorm_bwd_ws_floats(rows, H):
 def add_rowbcast(x, add, mod, out):
     lib = _lib.load()
     rows, cols = out.shape
-    check(lib.r3d_add_rowbcast(_p(x), _ld(x) if x is not None else 0, _p(add), _ld(add), mod, _p(out), _ld(out), rows, cols,
+    check(lib.r3d_add_rowbcast(_p(x), _ld0(x), _p(add), _ld(add), mod, _p(out), _ld(out), rows, cols,
                                _stream()), "r3d_add_rowbcast")
 
 
@@ -873,10 +854,10 @@ def losses_fwd_bwd(seg, act, dur, ld_dur, past_label, target, target_dur, B, S, 
     if ws is None:
         ws = torch.zeros(need, dtype=torch.float32, device=act.device)
     assert ws.numel() >= need
-    check(lib.r3d_losses_fwd_bwd(_p(seg), _ld(seg) if seg is not None else 0, _p(act), _ld(act), _p(dur), ld_dur,
+    check(lib.r3d_losses_fwd_bwd(_p(seg), _ld0(seg), _p(act), _ld(act), _p(dur), ld_dur,
                                  _p(past_label), _p(target), _p(target_dur), B, S, Q, K, pad_idx, exclude_idx,
                                  1 if val_mode else 0, _p(dur_den), grad_scale, _p(d_seg),
-                                 _ld(d_seg) if d_seg is not None else 0, _p(d_act), _ld(d_act) if d_act is not None else 0,
+                                 _ld0(d_seg), _p(d_act), _ld0(d_act),
                                  _p(d_dur), ld_ddur, _p(loss_out), _p(counts), _p(ws), _p(tick_a), _p(tick_b), _stream()),
           "r3d_losses_fwd_bwd")
 
@@ -893,10 +874,10 @@ def losses_fwd_bwd_kseg(seg, act, dur, ld_dur, past_label, target, target_dur, B
     if ws is None:
         ws = torch.zeros(need, dtype=torch.float32, device=act.device)
     assert ws.numel() >= need
-    check(lib.r3d_losses_fwd_bwd_kseg(_p(seg), _ld(seg) if seg is not None else 0, _p(act), _ld(act), _p(dur), ld_dur,
+    check(lib.r3d_losses_fwd_bwd_kseg(_p(seg), _ld0(seg), _p(act), _ld(act), _p(dur), ld_dur,
                                       _p(past_label), _p(target), _p(target_dur), B, S, Q, K, Kseg, pad_idx, exclude_idx,
                                       1 if val_mode else 0, _p(dur_den), grad_scale, _p(d_seg),
-                                      _ld(d_seg) if d_seg is not None else 0, _p(d_act), _ld(d_act) if d_act is not None else 0,
+                                      _ld0(d_seg), _p(d_act), _ld0(d_act),
                                       _p(d_dur), ld_ddur, _p(loss_out), _p(counts), _p(ws), _p(tick_a), _p(tick_b), _stream()),
           "r3d_losses_fwd_bwd_kseg")
 
@@ -1246,7 +1227,7 @@ def posenc_fwd(x, table, S, y, *, drop_mask=None, drop_scale=1.0):
 
 def posenc_bwd(dy, dx, *, drop_mask=None, drop_scale=1.0, gate=None):
     rows, H = dy.shape
-    check(_lib.load().r3d_posenc_bwd(_p(dy), _ld(dy), _p(drop_mask), drop_scale, _p(gate), _ld(gate) if gate is not None else 0,
+    check(_lib.load().r3d_posenc_bwd(_p(dy), _ld(dy), _p(drop_mask), drop_scale, _p(gate), _ld0(gate),
                                      _p(dx), _ld(dx), rows, H, _stream()), "r3d_posenc_bwd")
 
 
@@ -1512,8 +1493,8 @@ def tconv_fwd(x, v, s, bias, S, dilation, y, *, p_out=None, drop_mask=None, drop
     rows = x.shape[0]
     assert x.shape[1] == c_in and tuple(y.shape) == (rows, c_out) and (drop_mask is None or drop_mask.numel() == rows * c_out)
     check(_lib.load().r3d_tconv_fwd(_p(x), _ld(x), _p(v), _p(s), _p(bias), rows, S, c_in, c_out, dilation, _p(p_out),
-                                    _ld(p_out) if p_out is not None else 0, _p(y), _ld(y), _p(drop_mask), drop_scale, _p(res),
-                                    _ld(res) if res is not None else 0, _p(out), _ld(out) if out is not None else 0, _stream()),
+                                    _ld0(p_out), _p(y), _ld(y), _p(drop_mask), drop_scale, _p(res),
+                                    _ld0(res), _p(out), _ld0(out), _stream()),
           "r3d_tconv_fwd")
 
 
@@ -1531,7 +1512,7 @@ def tconv_dx(dz, v, s, S, dilation, dx, *, res=None, gate=None):
     rows = dz.shape[0]
     assert dz.shape[1] == c_out and tuple(dx.shape) == (rows, c_in)
     check(_lib.load().r3d_tconv_dx(_p(dz), _ld(dz), _p(v), _p(s), rows, S, c_in, c_out, dilation, _p(res),
-                                   _ld(res) if res is not None else 0, _p(gate), _ld(gate) if gate is not None else 0, _p(dx),
+                                   _ld0(res), _p(gate), _ld0(gate), _p(dx),
                                    _ld(dx), _stream()), "r3d_tconv_dx")
 
 
@@ -1562,7 +1543,7 @@ def ce_rows_fwd_bwd(logits, target, pad_idx, loss_out, counts, d_logits=None):
     assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == rows
     assert loss_out.numel() == 4 and counts.numel() == 4 and counts.dtype == torch.int64
     check(_lib.load().r3d_ce_rows_fwd_bwd(_p(logits), _ld(logits), _p(target), rows, Cc, pad_idx, _p(loss_out), _p(counts),
-                                          _p(d_logits), _ld(d_logits) if d_logits is not None else 0, _stream()),
+                                          _p(d_logits), _ld0(d_logits), _stream()),
           "r3d_ce_rows_fwd_bwd")
 
 
@@ -1685,7 +1666,7 @@ def focal_rows(pred, gold, pad_idx, *, exclude_idx=None, alpha=1.0, gamma=2.0, p
     check(_lib.load().r3d_focal_rows(_p(_f32(pred, "pred")), _ld(pred), _p(gold), N, Cc, int(pad_idx),
                                      0 if exclude_idx is None else 1, 0 if exclude_idx is None else int(exclude_idx),
                                      float(alpha), float(gamma), float(penalty_weight), _p(ws), _p(loss_out), _p(flags),
-                                     _p(counts), _p(d_loss), float(gscale), _p(d_pred), _ld(d_pred) if d_pred is not None else 0,
+                                     _p(counts), _p(d_loss), float(gscale), _p(d_pred), _ld0(d_pred),
                                      1 if add else 0, _stream()), "r3d_focal_rows")
 
 
@@ -1845,7 +1826,7 @@ def l3mix(seg, past_label, l3_flags, pad_idx, l3, lc, loss3, wf, ws, out, *, d_s
         assert _f32(d_seg, "d_seg").shape == (N, Kseg)
     ra, ca = d_actdur.shape if d_actdur is not None else (0, 0)
     check(_lib.load().r3d_l3mix(_p(_f32(seg, "seg")), _ld(seg), _p(past_label), _p(l3_flags), N, Kseg, int(pad_idx), _p(l3),
-                                _p(lc), _p(loss3), _p(wf), _p(d_seg), _ld(d_seg) if d_seg is not None else 0,
+                                _p(lc), _p(loss3), _p(wf), _p(d_seg), _ld0(d_seg),
                                 _p(None if d_actdur is None else _f32(d_actdur, "d_actdur")), ra, ca,
-                                _ld(d_actdur) if d_actdur is not None else 0, _p(l2_flags), _p(ws), _p(out), _stream()),
+                                _ld0(d_actdur), _p(l2_flags), _p(ws), _p(out), _stream()),
           "r3d_l3mix")
