@@ -8,6 +8,8 @@
 // same as the fp32 MFMA path -- tests/test_kernels_gpu.py::test_gemm_bf16x3_*).  6 MFMAs of K = 16 replace 8 of K = 2:
 // 2.7x less matrix-core time, which turns both GEMMs from MFMA-bound into HBM-bound kernels.
 // Selected per problem by r3d_gemm_desc::prec = 1 (the engine sets it for the depth projection only).
+// Every kernel of this file is pinned at small shapes by tests/test_gemm_bf3_gpu.py over tests/gemm_bf3_cases.py, which mirrors
+// the slab, k-step and grid arithmetic below (nt_slab_steps, nt_grid, tn_grid, tn_steps there): change both together.
 #include <type_traits>
 #include "common.h"
 #include "../../include/r3d_hip.h"

@@ -900,6 +900,7 @@ R3D_EXPORT int r3d_gemm_plan(r3d_gemm_desc* d) {
         d->alpha == 1.0f && (d->lda & 3) == 0 && (d->ldb & 3) == 0 && r3d_aligned16(d->A) && r3d_aligned16(d->B)) {
         // long-K NT product on the bf16 matrix cores (gemm_bf3.hip): 64 x 64 tiles while they are few, 128 x 128 beyond;
         // as many K-splits as fill the chip once (one workgroup per CU), each a multiple of 64 deep
+        // (this rule and the arithmetic below are mirrored by plan_nt() in tests/gemm_bf3_cases.py: change both together)
         const long t64 = (long)r3d_cdiv(d->M, 64) * r3d_cdiv(d->N, 64);
         const int tl = t64 <= 16 ? 8 : 9;
         const long tiles = tl == 8 ? t64 : (long)r3d_cdiv(d->M, 128) * r3d_cdiv(d->N, 128);

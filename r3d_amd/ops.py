@@ -59,9 +59,11 @@ class GemmWorkspace:
 
 def _fill_desc(d, layout, a, b, c, *, bias=None, act=0, pre_out=None, a_add=None, a_add_mod=0, a_row_xor=0, b_add=None,
                b_add_mod=0, drop_mask=None, drop_scale=1.0, aux=None, mul=0, res1=None, res2=None, alpha=1.0,
-               accumulate=False, c_row_xor=0, bias_grad=None, prec=0):
-    """Fills the problem and epilogue fields of a GemmDesc (not tile / split).  Returns (M, N, K)."""
-    _f32(a, "A"), _f32(b, "B"), _f32(c, "C")
+               accumulate=False, c_row_xor=0, bias_grad=None, prec=0, on_device=True):
+    """Fills the problem and epilogue fields of a GemmDesc (not tile / split).  Returns (M, N, K).
+    on_device=False (gemm_planned_tile only: nothing is launched) takes host tensors as well."""
+    if on_device:
+        _f32(a, "A"), _f32(b, "B"), _f32(c, "C")
     if layout == GEMM_NT:
         M, K = a.shape
         N = b.shape[0]
@@ -134,6 +136,7 @@ def gemm(layout, a, b, c, *, ws=None, tile=0, splitk=0, defer_reduce=False, adam
             d.splitk, d.k_per_split = 1, K
         else:
             q = 64 if d.tile == 8 else (32 if d.tile in (9, 11) else 16)     # the bf16x3 NT kernels step K by 64 / 32
+            # (for tiles 8, 9, 11 mirrored by nt_split() in tests/gemm_bf3_cases.py: change both together)
             kps = ((K + splitk - 1) // splitk + q - 1) // q * q
             d.splitk, d.k_per_split = (K + kps - 1) // kps, kps
             if d.splitk < 2:
@@ -151,9 +154,10 @@ def gemm(layout, a, b, c, *, ws=None, tile=0, splitk=0, defer_reduce=False, adam
 
 
 def gemm_planned_tile(layout, a, b, c, **epi):
-    """The tile r3d_gemm_plan picks for this product (no launch)."""
+    """The tile r3d_gemm_plan picks for this product (no launch; the tensors may live on the host: the planner reads shapes,
+    leading dimensions and alignments only)."""
     d = GemmDesc()
-    _fill_desc(d, layout, a, b, c, **epi)
+    _fill_desc(d, layout, a, b, c, on_device=False, **epi)
     check(_lib.load().r3d_gemm_plan(C.byref(d)), "r3d_gemm_plan")
     return int(d.tile)
 
@@ -172,7 +176,7 @@ def gemm_bf3_nt_pair(a1, b1, c1, ws1, a2, b2, c2, ws2):
         return None
     if any(t.data_ptr() % 16 or t.stride(0) % 4 for t in (a2, b2)):      # (the bf16x3 kernel loads 16-byte row segments)
         return None
-    spare = -d1.splitk % 8
+    spare = -d1.splitk % 8                      # (from here mirrored by pair_split() in tests/gemm_bf3_cases.py)
     if spare == 0:
         return None
     kps2 = ((K2 + spare - 1) // spare + 63) // 64 * 64

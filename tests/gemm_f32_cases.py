@@ -10,7 +10,7 @@ One `Case` is one launch (an "epi" case is the same launch repeated over act x m
             xor        c_row_xor = 1 with res1 (test_gemm_c_row_xor_is_pair_swap)
             adam       the AdamW epilogue (r3d_gemm_desc::adam_*), tile 0 = the tile ops.gemm picks
     layout  0 NT a[M,K] b[N,K]; 1 NN a[M,K] b[K,N]; 2 TN a[K,M] b[K,N]
-    tile    1..5 (launch_layout's cases); the bf16x3 tiles and the panel kernels are not in this table
+    tile    1..5 (launch_layout's cases); the bf16x3 tiles and the panel kernels are not in this table (tests/gemm_bf3_cases.py has 7 to 12)
     splitk  what is passed to ops.gemm; `nsplits` gives the number of slabs that makes
     pad     0 or 3: operand leading dimension = columns + pad (3: not a multiple of 4 -> the scalar-load twin)
     epi     frozenset of extra operand names on top of the kind: a_add, a_row_xor, b_add
