@@ -19,6 +19,7 @@
 #ifndef R3D_HIP_H
 #define R3D_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -404,6 +405,34 @@ int r3d_mha_tiled_bwd(const float* q, int ldq, const float* k, int ldk, const fl
 /* 1 if the two calls above run an (Lq, Lk, dh) problem, else 0; host-only, the same test the launches apply before they
  * launch anything: Lq >= 1, Lk >= 1 and 1 <= dh <= 128 (forward and backward alike). */
 int r3d_mha_tiled_supported(int Lq, int Lk, int dh, int bwd);
+
+/* ---- split-key attention core (csrc/attention_splitk.hip): few queries against many keys --------------------------
+ * The same product once more, for the token-fusion decoder's cross-attention (n_query rows per clip against the S frames
+ * of the memory) past r3d_mha_core_*'s LDS: 1 <= Lq <= 16, Lk >= 1, 1 <= dh <= 128.  Operands, scale, key masks, the
+ * dropout keep-mask, o, lse [B][heads][Lq] and delta [B][heads][Lq] exactly as r3d_mha_tiled_*: the two pairs are
+ * interchangeable on the same buffers (a forward of one, the backward of the other).  The KEYS are spread over the chip:
+ * grid (ceil(Lk / chunk), heads, B) with chunk = r3d_mha_splitk_chunk(Lk, dh), a pure function of its arguments and a
+ * multiple of 64.  Forward: every workgroup writes its chunk maximum, chunk sum and unnormalised
+ * sum exp(s - m_c) keep drop_scale v to ws; a second launch merges the chunks in chunk order into o and lse.  Backward:
+ * every workgroup recomputes delta and P = exp(s - lse), writes dk and dv of its keys (each element once) and its dq
+ * partial to ws; a second launch sums the partials in chunk order and writes delta.  ws: r3d_mha_splitk_ws_floats(...)
+ * floats owned by the caller (bwd != 0: what r3d_mha_splitk_bwd needs), contents undefined on entry.  No atomics, no
+ * workgroup waits on another, every sum has a fixed order: results are bitwise reproducible.  No allocation, no host
+ * synchronisation.  A refused shape returns R3D_EINVAL before anything is launched.  A clip whose keys are all masked
+ * gives NaN rows, as r3d_mha_core_fwd does. */
+int r3d_mha_splitk_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                       const uint8_t* key_padding_mask, const int64_t* key_label, int pad_idx, const uint8_t* drop_mask,
+                       float drop_scale, float* o, int ldo, float* lse, float* ws, int B, int heads, int Lq, int Lk, int dh,
+                       void* stream);
+int r3d_mha_splitk_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                       const uint8_t* key_padding_mask, const int64_t* key_label, int pad_idx, const uint8_t* drop_mask,
+                       float drop_scale, const float* o, int ldo, const float* lse, const float* d_o, int lddo, float* delta,
+                       float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, float* ws, int B, int heads, int Lq,
+                       int Lk, int dh, void* stream);
+/* host-only: 1 if the two calls above run an (Lq, Lk, dh) problem; the keys per workgroup; the floats of ws. */
+int r3d_mha_splitk_supported(int Lq, int Lk, int dh, int bwd);
+int r3d_mha_splitk_chunk(int Lk, int dh);
+size_t r3d_mha_splitk_ws_floats(int B, int heads, int Lq, int Lk, int dh, int bwd);
 
 /* ---- fused decoder layer, one workgroup per clip (TransformerDecoderLayer.forward_post, model/extras/transformer.py:
  * 281-330; final decoder.norm :182-183; fc|fc_len head futr_safuser_tokenfusion.py:219-226) --------------------------

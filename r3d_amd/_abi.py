@@ -7,8 +7,8 @@ import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "r3d_hip.h")
 
-SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
-           "double": C.c_double}
+SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+           "float": C.c_float, "double": C.c_double}
 
 _INT = r"\(?\s*(-?\d+)\s*\)?"
 _DECL = r"((?:const\s+)?\w+(?:\s*\*(?:\s*const\b)?)*)\s*(\w+)"          # "<type> <name>"; the stars belong to the type

@@ -19,7 +19,7 @@ SOURCES = ["abi.hip", "gemm_f32.hip", "rowops.hip", "fusion.hip", "attention.hip
            "erank.hip", "posenc.hip", "gemm_bf3.hip", "gemm_ln.hip", "fuser_chain.hip", "decoder_chain.hip", "fuser3.hip", "clipcache.hip",
            "varyfuse.hip", "plainfuse.hip", "lstm.hip", "tconv.hip", "attention_tiled.hip", "qr_stream.hip", "supcon.hip",
            "temporal.hip", "afft.hip", "cnn.hip", "attention_xclip.hip", "l3mix.hip", "qr_fold_wy.hip",
-           "fuse3_seam.hip", "lstm_steps.hip"]
+           "fuse3_seam.hip", "lstm_steps.hip", "attention_splitk.hip"]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
          "-Wno-unused-function", "-Wno-pass-failed"]
 

@@ -18,11 +18,12 @@ __device__ __forceinline__ float4 lds4(const float* p) { return *reinterpret_cas
 
 // rows [row0, row0 + 64) x [0, dh) of a strided matrix -> LDS [64][DP + 4]; rows past L and columns past dh are zero.
 // 16-byte loads where the head's rows allow them (the engine's slices do), single floats otherwise (dh 5, odd offsets).
-template <int DP>
+// (ROWS: the split-key core, attention_splitk.hip, stages its 16 query rows with the same code.)
+template <int DP, int ROWS = TT>
 __device__ __forceinline__ void stage_tile(float* dst, const float* base, int ld, int row0, int L, int dh, int tid) {
     constexpr int LD = DP + 4;
     if (((reinterpret_cast<uintptr_t>(base) & 15u) | (ld & 3) | (dh & 3)) == 0) {
-        for (int e = tid; e < TT * DP / 4; e += 256) {
+        for (int e = tid; e < ROWS * DP / 4; e += 256) {
             const int r = e / (DP / 4), d = (e % (DP / 4)) * 4;
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
             if (row0 + r < L && d < dh) x = *reinterpret_cast<const float4*>(base + (size_t)(row0 + r) * ld + d);
@@ -30,7 +31,7 @@ __device__ __forceinline__ void stage_tile(float* dst, const float* base, int ld
         }
         return;
     }
-    for (int e = tid; e < TT * DP; e += 256) {
+    for (int e = tid; e < ROWS * DP; e += 256) {
         const int r = e / DP, d = e % DP;
         float x = 0.f;
         if (row0 + r < L && d < dh) x = base[(size_t)(row0 + r) * ld + d];

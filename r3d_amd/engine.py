@@ -91,16 +91,45 @@ def check_engine_shape(H, heads, Q, bn=False, vary=False, plain=False):
                          f"n_query * head width <= 1024 outputs per wave")
 
 
-def check_clip_shape(S, H, heads, Q, max_pos_len, train):
-    """Raises ValueError unless a clip length S runs (train: with the backward, whose attention core needs more LDS)."""
+CROSS_ROUTES = ("core", "splitk", "tiled")
+
+
+def cross_attention_route(Q, S, dh, train, long_clips):
+    """The kernels the decoder's cross-attention (Q queries against the S frames of a clip) runs through: "core"
+    (r3d_mha_core_*, wherever it admits the shape -- so a clip it admits launches the same kernels whatever the flag, as
+    engine_unsup.query_attention_route), past it and only with long_clips (opts --long_clips, read by the models into
+    r3d_long_clips) "splitk" (r3d_mha_splitk_*, csrc/attention_splitk.hip: Q <= 16) or "tiled" (r3d_mha_tiled_* with
+    Lq = Q: more queries), or None (refused)."""
+    if ops.mha_core_supported(Q, S, dh, train):
+        return "core"
+    if long_clips and ops.mha_splitk_supported(Q, S, dh, train):
+        return "splitk"
+    if long_clips and ops.mha_tiled_supported(Q, S, dh, train):
+        return "tiled"
+    return None
+
+
+def cross_route_supported(route, Q, S, dh, train):
+    """The named route runs the shape (FusionEngine.cross_route forces a route only where this holds)."""
+    if route not in CROSS_ROUTES:
+        raise ValueError(f"cross_route {route!r}: None or one of {CROSS_ROUTES}")
+    return getattr(ops, f"mha_{route}_supported")(Q, S, dh, train)
+
+
+def check_clip_shape(S, H, heads, Q, max_pos_len, train, long_clips=False):
+    """Raises ValueError unless a clip length S runs (train: with the backward, whose attention core needs more LDS).
+    long_clips: the routes past the core count (cross_attention_route)."""
     if S <= 0:
         raise ValueError(f"clip length {S}: at least one frame")
     if S > max_pos_len:
         raise ValueError(f"clip length {S} > max_pos_len {max_pos_len}: the rows of pos_embedding")
     dh = H // heads
-    if not ops.mha_core_supported(Q, S, dh, train):
+    if cross_attention_route(Q, S, dh, train, long_clips) is None:
+        hint, flagged = "", None if long_clips else cross_attention_route(Q, S, dh, train, True)
+        if flagged is not None:
+            hint = f" (the {'split-key' if flagged == 'splitk' else 'tiled'} core runs this shape: --long_clips)"
         raise ValueError(f"clip length {S} at head width {dh}: the cross-attention core's {'backward' if train else 'forward'} "
-                         f"keeps {Q} x {S} scores in LDS, past its 160 KiB")
+                         f"keeps {Q} x {S} scores in LDS, past its 160 KiB" + hint)
 
 
 ERANK_ROUTES = ("jacobi", "tall")
@@ -126,12 +155,12 @@ def check_erank_shape(B, S, H, route="jacobi"):
                      f"{max(N, H)}-long columns in LDS, past its 150 KiB (--erank_route tall admits it)")
 
 
-def max_clip_len(H, heads, Q, max_pos_len, train):
+def max_clip_len(H, heads, Q, max_pos_len, train, long_clips=False):
     """The longest clip check_clip_shape admits (the LDS bound grows monotonically with S)."""
     lo, hi = 0, max_pos_len
     while lo < hi:
         mid = (lo + hi + 1) // 2
-        if ops.mha_core_supported(Q, mid, H // heads, train):
+        if cross_attention_route(Q, mid, H // heads, train, long_clips) is not None:
             lo = mid
         else:
             hi = mid - 1
@@ -161,13 +190,26 @@ class _Shape:
         self.m1, self.r1, self.m2, self.r2, self.mf, self.rf = f(2 * N), f(2 * N), f(2 * N), f(2 * N), f(2 * N), f(2 * N)
         self.fused = f(N, H)
         self.tgt0 = torch.zeros(BQ, H, dtype=torch.float32, device=dev)
+        # the cross-attention's route (cross_attention_route): past the core no [B, heads, Q, S] probabilities are kept --
+        # lse per layer, one delta, and on the split-key route its chunk partials (forward and backward share them)
+        self.route = eng._cross_route(S, train)
+        dh = H // heads
         self.layers = []
         for _ in range(L):
             d = dict(sa_qkv=f(BQ, 3 * H), sa_o=f(BQ, H), p_sa=f(B, heads, Q, Q), t1_pre=f(BQ, H),
                      t1=f(BQ, H), m1=f(BQ), r1=f(BQ), caq=f(BQ, H), cakv=f(N, 2 * H), ca_o=f(BQ, H),
-                     p_ca=f(B, heads, Q, S), t2_pre=f(BQ, H), t2=f(BQ, H), m2=f(BQ), r2=f(BQ), ff1=f(BQ, 4 * H),
+                     t2_pre=f(BQ, H), t2=f(BQ, H), m2=f(BQ), r2=f(BQ), ff1=f(BQ, 4 * H),
                      t3_pre=f(BQ, H), t3=f(BQ, H), m3=f(BQ), r3=f(BQ))
+            if self.route == "core":
+                d["p_ca"] = f(B, heads, Q, S)
+            else:
+                d["lse_ca"] = f(B, heads, Q)
+            if self.route == "splitk":
+                d["ws_ca"] = f(max(ops.mha_splitk_ws_floats(B, heads, Q, S, dh, False),
+                                   ops.mha_splitk_ws_floats(B, heads, Q, S, dh, True) if train else 0))
             self.layers.append(d)
+        if self.route != "core" and train:
+            self.delta = f(B, heads, Q)
         self.tgtF, self.mF, self.rF = f(BQ, H), f(BQ), f(BQ)
         self.actdur = f(BQ, K + 1)
         self.seg = f(N, K)
@@ -340,6 +382,11 @@ class FusionEngine(EngineBase):
         # tall route: "wy" | "column" | None (erank.fold_pays).  Part of train()'s graph key; a loop of its own sets it
         # before the first step (a change rebuilds the route's buffers on the next forward, which must not be a replay)
         self.erank_fold = None
+        # the decoder's cross-attention past the core's LDS (cross_attention_route): opts --long_clips, read by the models
+        # into r3d_long_clips.  cross_route: None (by rule) or "core" | "splitk" | "tiled" -- forces that route wherever it
+        # runs the shape (tests run the long-clip launches at small shapes with it); set before the first step of a shape
+        self.long_clips = bool(getattr(module, "r3d_long_clips", False))
+        self.cross_route = None
         self.erank_max_sweeps = 16        # blocked (two-level) Jacobi: sweeps enqueued per step (8-10 are used; the rest no-op)
         # the Jacobi forward depends on the fused tokens only: it is enqueued on a second stream as soon as they exist (a
         # parallel branch of the step's hipGraph) and joined where its backward adds into the fuser's upstream gradient --
@@ -355,8 +402,16 @@ class FusionEngine(EngineBase):
         self._adam = None
 
     # ------------------------------------------------------------------------------------------------------
+    def _cross_route(self, S, train):
+        """The cross-attention route of an S-frame clip: by rule (cross_attention_route), or self.cross_route where that
+        route runs the shape."""
+        if self.cross_route is not None and cross_route_supported(self.cross_route, self.Q, S, self.dh, train):
+            return self.cross_route
+        return cross_attention_route(self.Q, S, self.dh, train, self.long_clips)
+
     def _admit(self, B, S, train):
-        check_clip_shape(S, self.H, self.heads, self.Q, self.max_pos_len, train)
+        forced = self.cross_route is not None and S > 0 and cross_route_supported(self.cross_route, self.Q, S, self.dh, train)
+        check_clip_shape(S, self.H, self.heads, self.Q, self.max_pos_len, train, self.long_clips or forced)
 
     def _train_masks(self, B, S):
         """train mode: score = |d(mean)/dx| averaged over (B,T) = the constant 1/(B*T*C) for every channel
@@ -397,6 +452,10 @@ class FusionEngine(EngineBase):
                 raise ValueError("erank_route 'tall' on a data-parallel or pixel-sharded engine: the tall rank route runs "
                                  "on one GPU; use erank_route 'jacobi'")
             check_erank_shape(B, S, self.H, self.erank_route)      # (before anything is enqueued, as _shape's own checks)
+        if (self.tp is not None or self.grad_hook is not None) and 0 < S <= self.max_pos_len and \
+                self._cross_route(S, need_grad) not in ("core", None):
+            raise ValueError(f"clip length {S} on a data-parallel or pixel-sharded engine: the cross-attention routes past the "
+                             f"core (--long_clips) run on one GPU")
         w = self._shape(B, S, need_grad)
         self._loss_pending = None          # (see losses(): a pending loss reduction never survives into another step)
         self._erank_join()                 # (a forward whose backward never ran: its sweep still reads the workspace)
@@ -533,7 +592,7 @@ class FusionEngine(EngineBase):
         else:
             ops.layernorm_fwd(w.dep_pre, a.p("depth_layernorm.weight"), a.p("depth_layernorm.bias"), w.dep, w.mean_d,
                               w.rstd_d, relu=True)
-        fused_dec = self.use_fused_decoder and ops.decoder_fused_supported(S, Q, H, heads)
+        fused_dec = self.use_fused_decoder and w.route == "core" and ops.decoder_fused_supported(S, Q, H, heads)
         if fused_dec:
             multi = False                     # the whole layer is one launch: nothing left to branch
         # One decoder layer on one stream: the query self-attention sub-layer depends on parameters only, the fuser block
@@ -640,6 +699,7 @@ class FusionEngine(EngineBase):
             self._erank_forward(w)
         w._er_forked = False
         self.last = dict(w=w, x_rgb=x_rgb, x_dep=x_dep, mask=mask, idx=idx, drop=drop, mode=mode, tp=tp, seam=seam, erank=er,
+                         key_labels=key_labels,
                          paired=paired, bn_training=bool(fw.get("bn_training", False)))
         if self.rank_stream is not None:
             # the data-set rank (rankstream.py): this batch's embeddings and fused tokens folded into the streaming QR,
@@ -782,7 +842,8 @@ class FusionEngine(EngineBase):
         return bool(self.use_fuser_chain and self._chain_shape_ok(w))
 
     def _dec_chain_ok(self, w):
-        return bool(self.use_decoder_chain and decoder_chain_shape_ok(w.B, w.S, self.H, self.Q, self.heads, self.L))
+        return bool(self.use_decoder_chain and w.route == "core" and
+                    decoder_chain_shape_ok(w.B, w.S, self.H, self.Q, self.heads, self.L))
 
     def _dec_chain(self, w, drop):
         """The argument block of the decoder chain kernel for this workspace (one per dropout state)."""
@@ -901,6 +962,32 @@ class FusionEngine(EngineBase):
         self._erank_fork(w)
         g3.launch()
 
+    def _cross_fwd(self, w, c, key_labels, drop_mask, dsc):
+        """The cross-attention core of one decoder layer on the workspace's route (cross_attention_route)."""
+        H, args = self.H, (w.B, self.heads, self.Q, w.S, self.dh)
+        q, k, v = c["caq"], c["cakv"][:, :H], c["cakv"][:, H:]
+        kw = dict(key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=drop_mask, drop_scale=dsc)
+        if w.route == "core":
+            ops.mha_core_fwd(q, k, v, c["p_ca"], c["ca_o"], *args, **kw)
+        elif w.route == "splitk":
+            ops.mha_splitk_fwd(q, k, v, c["ca_o"], c["lse_ca"], c["ws_ca"], *args, **kw)
+        else:
+            ops.mha_tiled_fwd(q, k, v, c["ca_o"], c["lse_ca"], *args, **kw)
+
+    def _cross_bwd(self, w, c, gl, key_labels, drop_mask, dsc):
+        """Its adjoint: past the core the probabilities are recomputed, so the forward's key labels are passed again."""
+        H, args = self.H, (w.B, self.heads, self.Q, w.S, self.dh)
+        q, k, v = c["caq"], c["cakv"][:, :H], c["cakv"][:, H:]
+        dq, dk, dv = gl["caq"], gl["cakv"][:, :H], gl["cakv"][:, H:]
+        if w.route == "core":
+            ops.mha_core_bwd(q, k, v, c["p_ca"], gl["cao"], dq, dk, dv, *args, drop_mask=drop_mask, drop_scale=dsc)
+            return
+        kw = dict(key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=drop_mask, drop_scale=dsc)
+        if w.route == "splitk":
+            ops.mha_splitk_bwd(q, k, v, c["ca_o"], c["lse_ca"], gl["cao"], w.delta, dq, dk, dv, c["ws_ca"], *args, **kw)
+        else:
+            ops.mha_tiled_bwd(q, k, v, c["ca_o"], c["lse_ca"], gl["cao"], w.delta, dq, dk, dv, *args, **kw)
+
     def _decoder_unfused(self, w, key_labels, dm, dsc, multi, main, s2, sa_block, paired=False):
         """The decoder composed from the GEMM / attention / LayerNorm entry points (any shape)."""
         a, H, Q, K, heads, dh = self.arena, self.H, self.Q, self.K, self.heads, self.dh
@@ -941,8 +1028,7 @@ class FusionEngine(EngineBase):
                 ops.layernorm_fwd(c["t3_pre"], a.p(pl + "norm3.weight"), a.p(pl + "norm3.bias"), c["t3"], c["m3"], c["r3"])
                 tgt = c["t3"]
                 continue
-            ops.mha_core_fwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], c["ca_o"], B, heads, Q, S, dh,
-                             key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=dm(f"ca_p{l}"), drop_scale=dsc)
+            self._cross_fwd(w, c, key_labels, dm(f"ca_p{l}"), dsc)
             if self._gln(BQ, H):      # out_proj -> dropout -> + tgt -> norm2 (transformer.py:304-306): one launch
                 ops.gemm_ln_fwd([dict(a=c["ca_o"], w=a.p(pl + "multihead_attn.out_proj.weight"),
                                       bias=a.p(pl + "multihead_attn.out_proj.bias"),
@@ -1369,9 +1455,7 @@ class FusionEngine(EngineBase):
             ln_bwd(f"d2_{l}", gl["t2"], c["t2_pre"], c["m2"], c["r2"], pl + "norm2.weight", pl + "norm2.bias", gl["t2pre"],
                    dy2=gl["t2b"] if split else None, dx2=gl["cap"], drop_mask=dm(f"d2_{l}", BQ, H), drop_scale=dsc)
             ops.gemm(GEMM_NN, gl["cap"], p("multihead_attn.out_proj.weight"), gl["cao"], ws=ws)
-            ops.mha_core_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c["p_ca"], gl["cao"], gl["caq"],
-                             gl["cakv"][:, :H], gl["cakv"][:, H:], B, heads, Q, S, dh, drop_mask=dmf(f"ca_p{l}"),
-                             drop_scale=dsc)
+            self._cross_bwd(w, c, gl, st["key_labels"], dmf(f"ca_p{l}"), dsc)
             wi = p("multihead_attn.in_proj_weight")
             if st.get("paired"):
                 break                          # one layer, one stream: continued below with paired launches

@@ -135,6 +135,7 @@ class FUTR(EngineOwner, nn.Module):
         self.num_decoder_layers = num_decoder_layers
         self.n_query = n_query
         self.args = args
+        self.r3d_long_clips = bool(getattr(args, "long_clips", False))    # (opts --long_clips: engine.cross_attention_route)
         if getattr(args, "input_type", "i3d_transcript") != "i3d_transcript":
             raise NotImplementedError("only input_type='i3d_transcript' is built (the 'gt' embedding branch of "
                                       "futr_safuser_tokenfusion.py:150-152,180-182 is not on the RGB+Depth path)")

@@ -657,6 +657,43 @@ def mha_tiled_bwd(q, k, v, o, lse, d_o, delta, dq, dk, dv, B, heads, Lq, Lk, dh,
                                 _ld(dk), _p(dv), _ld(dv), B, heads, Lq, Lk, dh, _stream()), "r3d_mha_tiled_bwd")
 
 
+def mha_splitk_supported(Lq, Lk, dh, bwd):
+    """mha_splitk_fwd (bwd False) / mha_splitk_bwd (bwd True) runs an (Lq, Lk, dh) problem: the launches' own check."""
+    return bool(_lib.load().r3d_mha_splitk_supported(Lq, Lk, dh, 1 if bwd else 0))
+
+
+def mha_splitk_chunk(Lk, dh):
+    """Keys per workgroup of the split-key core: a multiple of 64 and a pure function of (Lk, dh)."""
+    return int(_lib.load().r3d_mha_splitk_chunk(Lk, dh))
+
+
+def mha_splitk_ws_floats(B, heads, Lq, Lk, dh, bwd):
+    """Floats of the workspace mha_splitk_fwd (bwd False) / mha_splitk_bwd (bwd True) needs."""
+    return int(_lib.load().r3d_mha_splitk_ws_floats(B, heads, Lq, Lk, dh, 1 if bwd else 0))
+
+
+def mha_splitk_fwd(q, k, v, o, lse, ws, B, heads, Lq, Lk, dh, *, kpm=None, key_labels=None, pad_idx=0, drop_mask=None,
+                   drop_scale=1.0):
+    """The split-key core (csrc/attention_splitk.hip), few queries against many keys: o and lse [B, heads, Lq] as
+    mha_tiled_fwd; ws holds mha_splitk_ws_floats(..., False) floats."""
+    lib = _lib.load()
+    assert ws.dtype == torch.float32 and ws.numel() >= lib.r3d_mha_splitk_ws_floats(B, heads, Lq, Lk, dh, 0)
+    check(lib.r3d_mha_splitk_fwd(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(kpm), _p(key_labels), pad_idx, _p(drop_mask),
+                                 drop_scale, _p(o), _ld(o), _p(lse), _p(ws), B, heads, Lq, Lk, dh, _stream()),
+          "r3d_mha_splitk_fwd")
+
+
+def mha_splitk_bwd(q, k, v, o, lse, d_o, delta, dq, dk, dv, ws, B, heads, Lq, Lk, dh, *, kpm=None, key_labels=None, pad_idx=0,
+                   drop_mask=None, drop_scale=1.0):
+    """Adjoint of mha_splitk_fwd (or of mha_tiled_fwd: the same o and lse): the forward's masks are passed again, delta
+    [B, heads, Lq] is filled, ws holds mha_splitk_ws_floats(..., True) floats."""
+    lib = _lib.load()
+    assert ws.dtype == torch.float32 and ws.numel() >= lib.r3d_mha_splitk_ws_floats(B, heads, Lq, Lk, dh, 1)
+    check(lib.r3d_mha_splitk_bwd(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(kpm), _p(key_labels), pad_idx, _p(drop_mask),
+                                 drop_scale, _p(o), _ld(o), _p(lse), _p(d_o), _ld(d_o), _p(delta), _p(dq), _ld(dq), _p(dk),
+                                 _ld(dk), _p(dv), _ld(dv), _p(ws), B, heads, Lq, Lk, dh, _stream()), "r3d_mha_splitk_bwd")
+
+
 # ----------------------------------------------------------------------------------------------------------
 # fused decoder layer
 # ----------------------------------------------------------------------------------------------------------

@@ -71,7 +71,9 @@ parser.add_argument("--pixel_shard", action="store_true", default=False,
 parser.add_argument("--long_clips", action="store_true", default=False,
                     help="depth-query / label-query models: run the decoder attentions of clips past the attention core's "
                          "limits through the tiled core (head width <= 128; the clip length is then bounded by max_pos_len "
-                         "alone).  Shorter clips launch the same kernels either way")
+                         "alone).  Fusion models (token fusion, BN-blend, activation-magnitude, plain SA-Fuser): run the "
+                         "decoder's cross-attention of clips past the core's LDS (1605 frames at head width 16, 933 at 128) "
+                         "through the split-key core.  Shorter clips launch the same kernels either way")
 parser.add_argument("--wide_rnn", action="store_true", default=False,
                     help="RNN model (model/rnn.py): admit hidden sizes past 256, up to 1024, by running the LSTM recurrence one "
                          "launch per time step with W_hh spread over the chip (csrc/lstm_steps.hip).  Hidden <= 256 launches "
