@@ -954,6 +954,23 @@ int r3d_supcon_fwd(const float* x, int ldx, const int64_t* labels, int bsz, int 
 int r3d_supcon_bwd(const float* x, int ldx, const int64_t* labels, int bsz, int N, int A, int D, int has_ignore,
                    int64_t ignore_index, float temperature, float base_temperature, int normalize, const float* ws,
                    const float* d_loss, float gscale, float* dx, int lddx, int add, void* stream);
+/* The wide route (opt-in): the same loss on rows of 1 <= D <= 2048 columns, the width walked in chunks of 256 columns.
+ * D <= 256 makes the launches of the pair above (the same bits).  257 <= D: the score tile is accumulated over the chunks
+ * before the statistics read it; normalize != 0 computes 1 / max(|x|, 1e-12) per row in a launch of its own and scales the
+ * scores by it (the rows are staged raw); the backward runs one workgroup per (64-row tile, 256-column chunk of dx), and
+ * with normalize stages dz in ws and finishes dx = (dz - z (z . dz)) / |x| in a row epilogue launch.  The conditions of
+ * the pair above hold for every launch.
+ * r3d_supcon_wide_ws_floats: the layout above (4 N + 4 floats), then with normalize and D > 256 dz [N, D], which the
+ *   backward writes (hence no const on its ws).  0 for a refused shape.
+ * r3d_supcon_wide_supported: 1 <= D <= 2048 (host-only).  A refused shape returns R3D_EINVAL before anything is enqueued. */
+int r3d_supcon_wide_supported(int D);
+int64_t r3d_supcon_wide_ws_floats(int N, int D, int normalize);
+int r3d_supcon_wide_fwd(const float* x, int ldx, const int64_t* labels, int bsz, int N, int A, int D, int has_ignore,
+                        int64_t ignore_index, float temperature, float base_temperature, int normalize, float* ws,
+                        float* loss_out, void* stream);
+int r3d_supcon_wide_bwd(const float* x, int ldx, const int64_t* labels, int bsz, int N, int A, int D, int has_ignore,
+                        int64_t ignore_index, float temperature, float base_temperature, int normalize, float* ws,
+                        const float* d_loss, float gscale, float* dx, int lddx, int add, void* stream);
 
 /* ---- temporal auxiliary losses (temporal.hip; reference utils.py :229-321, :493; train_unsupervised.py :34) --------------
  * Every call enqueues only; no allocation, no atomics, fixed-order reductions (the same call gives the same bits), no host

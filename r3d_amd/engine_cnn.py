@@ -104,9 +104,9 @@ class _Shape:
         if self.d_x is None:
             self.d_pooled, self.d_x = self._f(self.BQ, self.d_x0.shape[1]), self._f(*self.d_x0.shape)
 
-    def supcon_bufs(self, chain):
+    def supcon_bufs(self, chain, wide=False):
         if self.sc_ws is None:
-            self.sc_ws = self._f(ops.supcon_ws_floats(self.N))
+            self.sc_ws = self._f(ops.supcon_ws_floats(self.N, self.d_x0.shape[1], True, wide=wide))
             self.sc_loss = torch.zeros(1, dtype=torch.float32, device=self._dev)
         if chain and self.d_extra is None:
             self.d_extra = self._f(*self.d_x0.shape)
@@ -115,6 +115,8 @@ class _Shape:
 class CnnEngine(EngineBase):
     _Shape = _Shape
     defer_tail = True                       # a training forward() leaves everything behind x to losses() on the chain route
+    wide_supcon = False                     # --wide_supcon: the contrastive term runs the kernel's wide route (hidden > 256, the
+                                            # composed route); set before the first training step with supcon_weight > 0
 
     def __init__(self, module, device):
         self.H, self.Q, self.K = module.hidden_dim, POOL_ROWS, module.n_class
@@ -186,7 +188,7 @@ class CnnEngine(EngineBase):
     # ------------------------------------------------------------------------------------------------------
     def _supcon_kw(self):
         return dict(temperature=self.supcon_temperature, base_temperature=SUPCON_BASE_T, ignore_index=self.pad_idx,
-                    normalize=True)
+                    normalize=True, wide=self.wide_supcon)
 
     def losses(self, past_label, target, target_dur, with_grad=True, val_mode=False, tick=False):
         """The 3 losses + counters of train_unimodal.py:188-225 (exclude index 120).  Composed: one launch, fills d_seg /
@@ -198,9 +200,9 @@ class CnnEngine(EngineBase):
         w, K, a = st["w"], self.K, self.arena
         self._loss_pending = None
         supcon = bool(self.supcon_weight and with_grad and not val_mode)
-        if supcon and not ops.supcon_supported(self.H):          # (before anything of this step's losses is enqueued)
+        if supcon and not ops.supcon_supported(self.H, wide=self.wide_supcon):      # (before anything of this step's losses is enqueued)
             raise ValueError(f"hidden {self.H}: --supcon_weight on the CNN model contrasts its 'supcon' rows x [B*S, hidden], "
-                             f"and the supervised contrastive kernels take a width <= 256")
+                             f"and the supervised contrastive kernels take a width <= 256 (--wide_supcon: <= 2048)")
         lab = past_label.reshape(-1)
         st["supcon_labels"] = lab if supcon else None
         if st["deferred"] and with_grad and not val_mode:
@@ -209,7 +211,7 @@ class CnnEngine(EngineBase):
                                target_dur, self.pad_idx, EXCLUDE_CLASS_IDX, w.d_actdur, w.d_x0, w.loss_ws,
                                dur_den=self.dur_den, tick_a=self.step_t if tick else None)
             if supcon:
-                w.supcon_bufs(True)
+                w.supcon_bufs(True, self.wide_supcon)
                 ops.supcon_fwd(w.x, lab, w.N, w.N, w.sc_ws, w.sc_loss, **self._supcon_kw())
                 ops.supcon_bwd(w.x, lab, w.N, w.N, w.sc_ws, w.d_extra, gscale=self.supcon_weight, add=False,
                                **self._supcon_kw())
@@ -234,7 +236,7 @@ class CnnEngine(EngineBase):
                                 d_dur=w.d_actdur[:, K:] if with_grad else None, ld_ddur=K + 1, ws=w.loss_ws,
                                 tick_a=self.step_t if tick else None)
         if supcon:
-            w.supcon_bufs(False)
+            w.supcon_bufs(False, self.wide_supcon)
             ops.supcon_fwd(w.x, lab, w.N, w.N, w.sc_ws, w.sc_loss, **self._supcon_kw())
             w.loss[3:4].add_(w.sc_loss, alpha=self.supcon_weight)
         return w.loss, w.counts

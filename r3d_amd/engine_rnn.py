@@ -25,6 +25,7 @@ POOL_ROWS = 8                   # F.adaptive_avg_pool1d(tgt, 8) (model/rnn.py:97
 RNN_MIN_H, RNN_MAX_H = 8, 256   # the recurrence kernels' range (csrc/lstm.hip: W_hh of one direction in registers)
 RNN_WIDE_MAX_H = 1024           # with --wide_rnn: the stepwise recurrence (csrc/lstm_steps.hip: one launch per time step)
 SUPCON_MAX_H = 256              # the supervised contrastive kernel's column limit (csrc/supcon.hip)
+SUPCON_WIDE_MAX_H = 2048        # with --wide_supcon: its wide route's, past every hidden size this model admits
 
 SUPCON_BASE_T = 0.07            # SupConLoss's default base_temperature (loss/spc.py:69); the entry scripts pass temperature only
 
@@ -46,11 +47,12 @@ def lstm_route(H, wide):
     return None
 
 
-def check_rnn_shape(H, n_query=POOL_ROWS, erank_weight=0.0, wide=False, supcon_weight=0.0):
+def check_rnn_shape(H, n_query=POOL_ROWS, erank_weight=0.0, wide=False, supcon_weight=0.0, wide_supcon=False):
     """Raises ValueError unless the engine runs this model: hidden H in the recurrence kernels' range (up to RNN_WIDE_MAX_H
     with wide, opts --wide_rnn), n_query == 8 (the reference pools to 8 rows whatever n_query is, so its targets of n_query
     rows would not match the 8 outputs), no effective-rank penalty (defined on a fuser's token matrix; this model has none)
-    and no supervised contrastive term past its kernel's width.  Host-only, nothing is enqueued."""
+    and no supervised contrastive term past its kernel's width (256 columns; with wide_supcon, opts --wide_supcon, the
+    kernel's wide route takes every hidden size the model itself admits).  Host-only, nothing is enqueued."""
     if wide:
         if not (RNN_MIN_H <= H <= RNN_WIDE_MAX_H) or H % 8:
             raise ValueError(f"hidden {H}: with --wide_rnn the LSTM recurrence kernels take {RNN_MIN_H} <= hidden <= "
@@ -67,9 +69,10 @@ def check_rnn_shape(H, n_query=POOL_ROWS, erank_weight=0.0, wide=False, supcon_w
     if erank_weight:
         raise ValueError(f"erank_weight {erank_weight}: the effective-rank penalty needs a fuser's token matrix; the RNN "
                          f"model has none")
-    if supcon_weight and H > SUPCON_MAX_H:
+    if supcon_weight and H > (SUPCON_WIDE_MAX_H if wide_supcon else SUPCON_MAX_H):
         raise ValueError(f"supcon_weight {supcon_weight} at hidden {H}: the supervised contrastive kernel takes rows of at "
-                         f"most {SUPCON_MAX_H} columns (csrc/supcon.hip), so --supcon_weight needs hidden <= {SUPCON_MAX_H}")
+                         f"most {SUPCON_MAX_H} columns (csrc/supcon.hip), so --supcon_weight needs hidden <= {SUPCON_MAX_H}, "
+                         f"or --wide_supcon (its wide route: rows of at most {SUPCON_WIDE_MAX_H} columns)")
 
 
 def _arena_order(named):
@@ -112,7 +115,8 @@ class _Shape:
             self.d_y = [f(N, H), f(N, H)]
             self.dg = f(N, 4 * H)
             self.d_x0, self.d_x, self.d_pre = f(N, H), f(N, H), f(N, H)
-            self.sc_ws, self.sc_loss = f(ops.supcon_ws_floats(N)), torch.zeros(1, dtype=torch.float32, device=dev)
+            self.sc_ws = f(ops.supcon_ws_floats(N, H, True, wide=eng.wide_supcon))
+            self.sc_loss = torch.zeros(1, dtype=torch.float32, device=dev)
             if eng.steps:               # the stepwise backward's dc carry and transposed W_hh
                 self.lstm_ws = f(ops.lstm_steps_ws_floats(B, H))
 
@@ -120,6 +124,8 @@ class _Shape:
 class RnnEngine(EngineBase):
     _Shape = _Shape
     use_lstm_steps = None           # None: routed by lstm_route(); True: the stepwise kernels at any admitted hidden size
+    wide_supcon = False             # --wide_supcon: the contrastive term runs the kernel's wide route (hidden > 256); set before
+                                    # supcon_weight and before the first training step (the step's workspace is sized by it)
 
     def __init__(self, module, device):
         self.wide = bool(getattr(module, "r3d_wide_rnn", False))    # (opts --wide_rnn)
@@ -149,7 +155,7 @@ class RnnEngine(EngineBase):
 
     @supcon_weight.setter
     def supcon_weight(self, v):
-        check_rnn_shape(self.H, self.Q, wide=self.wide, supcon_weight=v)
+        check_rnn_shape(self.H, self.Q, wide=self.wide, supcon_weight=v, wide_supcon=self.wide_supcon)
         self._supcon_weight = v
 
     @property
@@ -199,7 +205,7 @@ class RnnEngine(EngineBase):
     # ------------------------------------------------------------------------------------------------------
     def _supcon_kw(self):
         return dict(temperature=self.supcon_temperature, base_temperature=SUPCON_BASE_T, ignore_index=self.pad_idx,
-                    normalize=True)
+                    normalize=True, wide=self.wide_supcon)
 
     def losses(self, past_label, target, target_dur, with_grad=True, val_mode=False, tick=False):
         """The 3 losses + counters of train_unimodal.py:188-225 (exclude index 120) in one launch; fills d_seg / d_actdur.

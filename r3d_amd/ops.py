@@ -1591,13 +1591,21 @@ def ce_rows_fwd_bwd(logits, target, pad_idx, loss_out, counts, d_logits=None):
 # ----------------------------------------------------------------------------------------------------------
 # supervised contrastive loss (csrc/supcon.hip)
 # ----------------------------------------------------------------------------------------------------------
-def supcon_supported(D):
-    """supcon_fwd / supcon_bwd run rows of width D (host-only; the launches' own check)."""
-    return bool(_lib.load().r3d_supcon_supported(int(D)))
+def supcon_supported(D, wide=False):
+    """supcon_fwd / supcon_bwd run rows of width D (host-only; the launches' own check).  wide: the opt-in route of up to
+    2048 columns."""
+    lib = _lib.load()
+    return bool(lib.r3d_supcon_wide_supported(int(D)) if wide else lib.r3d_supcon_supported(int(D)))
 
 
-def supcon_ws_floats(N):
-    return int(_lib.load().r3d_supcon_ws_floats(int(N)))
+def supcon_ws_floats(N, D=None, normalize=False, wide=False):
+    """Floats of the pair's workspace.  wide: of the wide route at width D, which with normalize and D > 256 stages the
+    backward's dz [N, D] behind the 4 N + 4 statistics."""
+    if not wide:
+        return int(_lib.load().r3d_supcon_ws_floats(int(N)))
+    if D is None:
+        raise ValueError("supcon_ws_floats(wide=True) needs the row width D")
+    return int(_lib.load().r3d_supcon_wide_ws_floats(int(N), int(D), 1 if normalize else 0))
 
 
 def _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature, normalize):
@@ -1608,20 +1616,35 @@ def _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature,
             0 if ignore_index is None else int(ignore_index), float(temperature), float(base_temperature), 1 if normalize else 0)
 
 
-def supcon_fwd(x, labels, bsz, A, ws, loss_out, *, temperature=0.07, base_temperature=0.07, ignore_index=None, normalize=False):
+def _supcon_entry(name, wide, x, ws, normalize):
+    """(the C entry, its name) of the narrow or the wide pair; the wide one's larger workspace is checked here, since the
+    library sees a pointer only."""
+    if not wide:
+        return getattr(_lib.load(), "r3d_supcon_" + name), "r3d_supcon_" + name
+    need = supcon_ws_floats(x.shape[0], x.shape[1], normalize, wide=True)
+    if need and ws.numel() < need:
+        raise ValueError(f"supcon_{name}(wide=True): ws has {ws.numel()} floats, rows {tuple(x.shape)} need {need}")
+    return getattr(_lib.load(), "r3d_supcon_wide_" + name), "r3d_supcon_wide_" + name
+
+
+def supcon_fwd(x, labels, bsz, A, ws, loss_out, *, temperature=0.07, base_temperature=0.07, ignore_index=None, normalize=False,
+               wide=False):
     """x [N, D] (any row stride): the contrast rows, row r labelled labels[r % bsz] (None: r % bsz), the first A anchors.
-    Fills ws (supcon_ws_floats(N) floats: lse, positive mean, P, 1/|x|, anchor count) and loss_out[0]; enqueue only."""
+    Fills ws (supcon_ws_floats(N) floats: lse, positive mean, P, 1/|x|, anchor count) and loss_out[0]; enqueue only.
+    wide: the route of up to 2048 columns, with ws of supcon_ws_floats(N, D, normalize, wide=True) floats."""
     head = _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature, normalize)
-    check(_lib.load().r3d_supcon_fwd(*head, _p(_f32(ws, "ws")), _p(_f32(loss_out, "loss_out")), _stream()), "r3d_supcon_fwd")
+    fn, what = _supcon_entry("fwd", wide, x, ws, normalize)
+    check(fn(*head, _p(_f32(ws, "ws")), _p(_f32(loss_out, "loss_out")), _stream()), what)
 
 
 def supcon_bwd(x, labels, bsz, A, ws, dx, *, d_loss=None, gscale=1.0, add=False, temperature=0.07, base_temperature=0.07,
-               ignore_index=None, normalize=False):
+               ignore_index=None, normalize=False, wide=False):
     """dx [N, D] = (dx if add else 0) + gscale * d_loss[0] * d loss / d x from the forward's arguments and its ws; d_loss is
-    a device scalar (None: 1), so a graphed step needs no read-back."""
+    a device scalar (None: 1), so a graphed step needs no read-back.  wide: as in supcon_fwd (with normalize and D > 256 the
+    staging part of ws is written)."""
     head = _supcon_head(x, labels, bsz, A, ignore_index, temperature, base_temperature, normalize)
-    check(_lib.load().r3d_supcon_bwd(*head, _p(_f32(ws, "ws")), _p(d_loss), float(gscale), _p(_f32(dx, "dx")), _ld(dx),
-                                     1 if add else 0, _stream()), "r3d_supcon_bwd")
+    fn, what = _supcon_entry("bwd", wide, x, ws, normalize)
+    check(fn(*head, _p(_f32(ws, "ws")), _p(d_loss), float(gscale), _p(_f32(dx, "dx")), _ld(dx), 1 if add else 0, _stream()), what)
 
 
 # ----------------------------------------------------------------------------------------------------------

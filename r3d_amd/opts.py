@@ -89,7 +89,13 @@ parser.add_argument("--supcon_weight", type=float, default=0.0,
                          "main_nturgbd.py:137, and leaves its use commented out).  Build-defined: the rows are L2-normalised "
                          "and padded frames skipped because unnormalised rnn_fc outputs are exactly the input on which the "
                          "reference's SupConLoss returns nan, so the parity of this term is pinned only against the float64 "
-                         "restatement (tests/supcon_oracle.py).  The other loops refuse a non-zero value")
+                         "restatement (tests/supcon_oracle.py).  The rows are hidden wide, and the kernel takes 256 columns: a wider "
+                         "model needs --wide_supcon as well.  The other loops refuse a non-zero value")
+parser.add_argument("--wide_supcon", action="store_true", default=False,
+                    help="RNN loop (train_unimodal) only: run the --supcon_weight term through the contrastive kernel's wide "
+                         "route (csrc/supcon.hip: rows of up to 2048 columns walked in chunks of 256), which admits the term at "
+                         "every hidden size the model itself admits (RNN: past 256 with --wide_rnn, up to 1024; CNN: up to "
+                         "1024).  Hidden <= 256 launches the same kernels either way")
 parser.add_argument("--gaze_dim", type=int, default=2,
                     help="three-modality model (model/futr_safuser_tokenfusion3.py) only: values per frame of the gaze track "
                          "(1 to 8; the gaze data set yields [S, 2] tracks)")

@@ -20,7 +20,8 @@ Build-defined addition: ``--supcon_weight W`` (default 0.0: none of the followin
 temperature=args.temperature, normalize=True, ignore_index=pad_idx) over the B * S rows of ``outputs['supcon']`` with the
 labels ``past_label.view(-1)`` -- the use main_nturgbd.py:137 prepares and the reference's loop leaves commented out --
 to the step's loss, inside the step (the engine's losses / backward; the CNN model's rows are x, hidden <= 256); the epoch's ``Loss`` includes it and one
-``supcon loss`` line follows the ``seg loss`` line.  validate() is unchanged.
+``supcon loss`` line follows the ``seg loss`` line.  validate() is unchanged.  ``--wide_supcon`` runs the term through the
+kernel's wide route, which admits it at hidden > 256 (RNN with --wide_rnn, and CNN, up to 1024).
 """
 import torch
 import torch.distributed as dist
@@ -39,13 +40,13 @@ def _unwrap(model):
     return unwrap(model, (FUTR, FUTRCnn), "r3d_amd.train_unimodal drives r3d_amd.model.rnn.FUTR or r3d_amd.model.cnn.FUTR")
 
 
-def _check_shape(core, erank_weight, supcon_weight=0.0):
+def _check_shape(core, erank_weight, supcon_weight=0.0, wide_supcon=False):
     """The model's own admission rule, on the host, before anything is enqueued."""
     if isinstance(core, FUTRCnn):
         check_cnn_shape(core.hidden_dim, core.n_query, core.n_class, erank_weight, input_dim=core.input_embed.in_features)
     else:
         check_rnn_shape(core.hidden_dim, core.n_query, erank_weight, wide=getattr(core, "r3d_wide_rnn", False),
-                        supcon_weight=supcon_weight)
+                        supcon_weight=supcon_weight, wide_supcon=wide_supcon)
 
 
 def _to_dev(data, device):
@@ -86,7 +87,9 @@ def validate(model, val_loader, criterion, pad_idx, device):
 
 def train(args, model, train_loader, optimizer, scheduler, criterion, model_save_path, pad_idx, device, val_loader, seed):
     core = _unwrap(model)
-    _check_shape(core, float(getattr(args, "erank_weight", 0.0) or 0.0), float(getattr(args, "supcon_weight", 0.0) or 0.0))
+    wide_supcon = bool(getattr(args, "wide_supcon", False))
+    _check_shape(core, float(getattr(args, "erank_weight", 0.0) or 0.0), float(getattr(args, "supcon_weight", 0.0) or 0.0),
+                 wide_supcon)
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise NotImplementedError("r3d_amd.train_unimodal trains its model on one GPU; multi-rank torch.distributed "
                                   "runs of it are not supported")
@@ -94,6 +97,7 @@ def train(args, model, train_loader, optimizer, scheduler, criterion, model_save
     model.train()
     eng = core.engine()
     # --supcon_weight: the supervised contrastive term on the 'supcon' output, part of every step (graphed or eager)
+    eng.wide_supcon = wide_supcon          # (before the weight: the RNN engine's setter checks the shape against it)
     eng.supcon_weight = float(getattr(args, "supcon_weight", 0.0) or 0.0)
     eng.supcon_temperature = float(getattr(args, "temperature", 0.07))
     min_batch = getattr(args, "min_batch", 8)
