@@ -21,9 +21,8 @@
 //             with the key as the row) and its dq partial to ws; a second launch sums the partials in chunk order and
 //             writes delta.
 // No atomics, no workgroup waits on another, every sum has a fixed order: the same call gives the same bits.
-#include "common.h"
-#include "tile_mma.h"
-#include "../../include/r3d_hip.h"
+// The argument block, the key mask and the host check are attention_lse.h's, shared with the tiled core.
+#include "attention_lse.h"
 
 #ifndef R3D_SPLITK_CHUNK
 #define R3D_SPLITK_CHUNK 128       // keys per workgroup (a multiple of 64); see DESIGN.md for the values tried
@@ -33,34 +32,6 @@ namespace r3d {
 
 constexpr int SKQ = 16;            // query rows of the one column block
 constexpr int PLD = 20;            // row stride of a wave's 16 x 16 transposition tile
-
-struct SplitkArgs {
-    const float *q, *k, *v;
-    int ldq, ldk, ldv;
-    const uint8_t* kpm;
-    const int64_t* key_label;
-    int pad_idx;
-    const uint8_t* drop;
-    float drop_scale;
-    float* o;           // forward: written; backward: read
-    int ldo;
-    float* lse;         // [B][heads][Lq]
-    const float* d_o;
-    int lddo;
-    float* delta;       // [B][heads][Lq]
-    float *dq, *dk, *dv;
-    int lddq, lddk, lddv;
-    float* ws;
-    int B, heads, Lq, Lk, dh;
-    int chunk, nchunk;
-    float scale;
-};
-
-__device__ __forceinline__ bool sk_key_masked(const SplitkArgs& a, int b, int j) {
-    if (j >= a.Lk) return true;
-    const size_t e = (size_t)b * a.Lk + j;
-    return (a.kpm && a.kpm[e]) || (a.key_label && a.key_label[e] == (int64_t)a.pad_idx);
-}
 
 // delta of query row q: 4 lanes per row (part = 0..3), the order of the tiled dq kernel
 __device__ __forceinline__ float sk_delta(const float* dob, int lddo, const float* ob, int ldo, int q, int Lq, int dh, int part) {
@@ -80,7 +51,7 @@ __device__ __forceinline__ void park_acc(float* Wa, const f32x4 (&acc)[DP / 16],
 }
 
 template <int DP>
-__global__ __launch_bounds__(256) void mha_splitk_fwd_kernel(const SplitkArgs a) {
+__global__ __launch_bounds__(256) void mha_splitk_fwd_kernel(const LseArgs a) {
     constexpr int LD = DP + 4, NT = DP / 16;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Qs = lds;                    // [16][LD]
@@ -112,7 +83,7 @@ __global__ __launch_bounds__(256) void mha_splitk_fwd_kernel(const SplitkArgs a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = k0 + 16 * w + 4 * kq + r;
-            masked[r] = sk_key_masked(a, b, j);
+            masked[r] = key_masked(a, b, j);
             keep[r] = (a.drop && c < Lq && j < Lk) ? a.drop[drow + j] : (uint8_t)1;
         }
         __syncthreads();
@@ -184,7 +155,7 @@ __global__ __launch_bounds__(256) void mha_splitk_fwd_kernel(const SplitkArgs a)
 }
 
 // o = sum_c acc_c exp(m_c - m) / sum_c l_c exp(m_c - m), lse = m + log l; one thread per output element, chunk order
-__global__ __launch_bounds__(256) void mha_splitk_fwd_combine_kernel(const SplitkArgs a) {
+__global__ __launch_bounds__(256) void mha_splitk_fwd_combine_kernel(const LseArgs a) {
     const int Lq = a.Lq, dh = a.dh, h = blockIdx.y, b = blockIdx.z;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= Lq * dh) return;
@@ -205,7 +176,7 @@ __global__ __launch_bounds__(256) void mha_splitk_fwd_combine_kernel(const Split
 }
 
 template <int DP>
-__global__ __launch_bounds__(256) void mha_splitk_bwd_kernel(const SplitkArgs a) {
+__global__ __launch_bounds__(256) void mha_splitk_bwd_kernel(const LseArgs a) {
     constexpr int LD = DP + 4, NT = DP / 16;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Qs = lds;                    // [16][LD]
@@ -253,7 +224,7 @@ __global__ __launch_bounds__(256) void mha_splitk_bwd_kernel(const SplitkArgs a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = k0 + 16 * w + 4 * kq + r;
-            live[r] = !sk_key_masked(a, b, j) && c < Lq;
+            live[r] = !key_masked(a, b, j) && c < Lq;
             keepb[r] = (a.drop && live[r]) ? a.drop[(bh * Lq + c) * Lk + j] : (uint8_t)1;
         }
         __syncthreads();
@@ -319,7 +290,7 @@ __global__ __launch_bounds__(256) void mha_splitk_bwd_kernel(const SplitkArgs a)
 }
 
 // dq = the chunks' partials summed in chunk order; block 0 of each (head, clip) also writes delta
-__global__ __launch_bounds__(256) void mha_splitk_bwd_reduce_kernel(const SplitkArgs a) {
+__global__ __launch_bounds__(256) void mha_splitk_bwd_reduce_kernel(const LseArgs a) {
     const int Lq = a.Lq, dh = a.dh, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
     const size_t bh = (size_t)b * a.heads + h;
     if (blockIdx.x == 0 && tid < 4 * SKQ) {                     // (wave 0, whole)
@@ -346,33 +317,17 @@ static int splitk_chunk(int /*Lk*/, int /*dh*/) {
     return R3D_SPLITK_CHUNK;
 }
 
-static int splitk_dp(int dh) { return dh <= 16 ? 16 : dh <= 32 ? 32 : dh <= 64 ? 64 : 128; }
-
 static size_t splitk_lds_bytes(int dp, bool bwd) {
     const size_t tiles = (size_t)((bwd ? 2 : 1) * SKQ + 2 * TT) * (dp + 4);
     return (tiles + (bwd ? 2 * 4 * SKQ * PLD + 2 * SKQ : 0)) * sizeof(float);
 }
 
-static int splitk_check(const SplitkArgs& a, bool bwd) {
-    if (!splitk_shape_ok(a.Lq, a.Lk, a.dh, bwd)) return R3D_EINVAL;
-    if (!a.q || !a.k || !a.v || !a.o || !a.lse || !a.ws) return R3D_EINVAL;
-    if (a.B <= 0 || a.heads <= 0 || a.B > 65535 || a.heads > 65535) return R3D_EINVAL;
-    const int H = a.heads * a.dh;
-    if (a.ldq < H || a.ldk < H || a.ldv < H || a.ldo < H) return R3D_EINVAL;
-    if (bwd && (!a.d_o || !a.delta || !a.dq || !a.dk || !a.dv || a.lddo < H || a.lddq < H || a.lddk < H || a.lddv < H))
-        return R3D_EINVAL;
-    return R3D_OK;
-}
-
 template <int DP>
-static int splitk_launch(const SplitkArgs& a, bool bwd, hipStream_t s) {
+static int splitk_launch(const LseArgs& a, bool bwd, hipStream_t s) {
     const size_t lds = splitk_lds_bytes(DP, bwd);
     const dim3 gc(a.nchunk, a.heads, a.B), ge(r3d_cdiv(a.Lq * a.dh, 256), a.heads, a.B), blk(256);
-    if (lds > 64 * 1024) {
-        hipError_t e = bwd ? hipFuncSetAttribute((const void*)mha_splitk_bwd_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                           : hipFuncSetAttribute((const void*)mha_splitk_fwd_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = allow_dynamic_lds(bwd ? (const void*)mha_splitk_bwd_kernel<DP> : (const void*)mha_splitk_fwd_kernel<DP>, lds);
+    if (e != hipSuccess) return (int)e;
     if (!bwd) {
         hipLaunchKernelGGL(mha_splitk_fwd_kernel<DP>, gc, blk, lds, s, a);     // chunk partials -> ws ...
         R3D_LAUNCH_CHECK();
@@ -387,14 +342,13 @@ static int splitk_launch(const SplitkArgs& a, bool bwd, hipStream_t s) {
     return R3D_OK;
 }
 
-static int splitk_dispatch(SplitkArgs& a, bool bwd, void* stream) {
-    int rc = splitk_check(a, bwd);
+static int splitk_dispatch(LseArgs a, bool bwd, void* stream) {
+    int rc = lse_admit(a, splitk_shape_ok(a.Lq, a.Lk, a.dh, bwd), bwd, true);
     if (rc != R3D_OK) return rc;
     a.chunk = splitk_chunk(a.Lk, a.dh);
     a.nchunk = r3d_cdiv(a.Lk, a.chunk);
-    a.scale = 1.0f / sqrtf((float)a.dh);
     hipStream_t s = (hipStream_t)stream;
-    switch (splitk_dp(a.dh)) {
+    switch (tile_dp(a.dh)) {
         case 16: return splitk_launch<16>(a, bwd, s);
         case 32: return splitk_launch<32>(a, bwd, s);
         case 64: return splitk_launch<64>(a, bwd, s);
@@ -420,12 +374,9 @@ R3D_EXPORT int r3d_mha_splitk_fwd(const float* q, int ldq, const float* k, int l
                                   const uint8_t* key_padding_mask, const int64_t* key_label, int pad_idx,
                                   const uint8_t* drop_mask, float drop_scale, float* o, int ldo, float* lse, float* ws, int B,
                                   int heads, int Lq, int Lk, int dh, void* stream) {
-    SplitkArgs a{};
-    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.kpm = key_padding_mask;
-    a.key_label = key_label; a.pad_idx = pad_idx; a.drop = drop_mask; a.drop_scale = drop_scale;
-    a.o = o; a.ldo = ldo; a.lse = lse; a.ws = ws;
-    a.B = B; a.heads = heads; a.Lq = Lq; a.Lk = Lk; a.dh = dh;
-    return splitk_dispatch(a, false, stream);
+    return splitk_dispatch(lse_args(q, ldq, k, ldk, v, ldv, key_padding_mask, key_label, pad_idx, drop_mask, drop_scale, o, ldo, lse,
+                                    nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, ws, B, heads, Lq, Lk, dh),
+                           false, stream);
 }
 
 R3D_EXPORT int r3d_mha_splitk_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
@@ -433,11 +384,7 @@ R3D_EXPORT int r3d_mha_splitk_bwd(const float* q, int ldq, const float* k, int l
                                   const uint8_t* drop_mask, float drop_scale, const float* o, int ldo, const float* lse,
                                   const float* d_o, int lddo, float* delta, float* dq, int lddq, float* dk, int lddk, float* dv,
                                   int lddv, float* ws, int B, int heads, int Lq, int Lk, int dh, void* stream) {
-    SplitkArgs a{};
-    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.kpm = key_padding_mask;
-    a.key_label = key_label; a.pad_idx = pad_idx; a.drop = drop_mask; a.drop_scale = drop_scale;
-    a.o = const_cast<float*>(o); a.ldo = ldo; a.lse = const_cast<float*>(lse); a.d_o = d_o; a.lddo = lddo; a.delta = delta;
-    a.dq = dq; a.lddq = lddq; a.dk = dk; a.lddk = lddk; a.dv = dv; a.lddv = lddv; a.ws = ws;
-    a.B = B; a.heads = heads; a.Lq = Lq; a.Lk = Lk; a.dh = dh;
-    return splitk_dispatch(a, true, stream);
+    return splitk_dispatch(lse_args(q, ldq, k, ldk, v, ldv, key_padding_mask, key_label, pad_idx, drop_mask, drop_scale, o, ldo, lse,
+                                    d_o, lddo, delta, dq, lddq, dk, lddk, dv, lddv, ws, B, heads, Lq, Lk, dh),
+                           true, stream);
 }

@@ -16,37 +16,10 @@
 //             dS = P o (dO V^T o keep * drop_scale - delta) * scale -> LDS, dQ += dS K.
 //     dkv     grid over KEY tiles (launched after dq: it reads delta): K / V resident, sweeps the query tiles with the
 //             TRANSPOSED products (K Q^T, V dO^T, so the key is the accumulator row): dV += P'^T dO, dK += dS^T Q.
-#include "common.h"
-#include "tile_mma.h"
-#include "../../include/r3d_hip.h"
+// The argument block, the key mask and the host check are attention_lse.h's, shared with the split-key core.
+#include "attention_lse.h"
 
 namespace r3d {
-
-struct TiledArgs {
-    const float *q, *k, *v;
-    int ldq, ldk, ldv;
-    const uint8_t* kpm;
-    const int64_t* key_label;
-    int pad_idx;
-    const uint8_t* drop;
-    float drop_scale;
-    float* o;           // forward: written; backward: read
-    int ldo;
-    float* lse;         // [B][heads][Lq]
-    const float* d_o;
-    int lddo;
-    float* delta;       // [B][heads][Lq]
-    float *dq, *dk, *dv;
-    int lddq, lddk, lddv;
-    int B, heads, Lq, Lk, dh;
-    float scale;
-};
-
-__device__ __forceinline__ bool key_masked(const TiledArgs& a, int b, int j) {
-    if (j >= a.Lk) return true;
-    const size_t e = (size_t)b * a.Lk + j;
-    return (a.kpm && a.kpm[e]) || (a.key_label && a.key_label[e] == (int64_t)a.pad_idx);
-}
 
 // accumulator tiles of wave w -> rows [row0 + 16w, ...) x [0, dh) of a strided matrix (rows past L are not written)
 template <int DP>
@@ -63,7 +36,7 @@ __device__ __forceinline__ void store_acc(const f32x4 (&acc)[DP / 16], float* ba
 }
 
 template <int DP>
-__global__ __launch_bounds__(256) void mha_tiled_fwd_kernel(const TiledArgs a) {
+__global__ __launch_bounds__(256) void mha_tiled_fwd_kernel(const LseArgs a) {
     constexpr int LD = DP + 4, NT = DP / 16;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Qs = lds;                    // [64][LD]
@@ -159,7 +132,7 @@ __global__ __launch_bounds__(256) void mha_tiled_fwd_kernel(const TiledArgs a) {
 }
 
 template <int DP>
-__global__ __launch_bounds__(256) void mha_tiled_bwd_dq_kernel(const TiledArgs a) {
+__global__ __launch_bounds__(256) void mha_tiled_bwd_dq_kernel(const LseArgs a) {
     constexpr int LD = DP + 4, NT = DP / 16;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Qs = lds;                    // [64][LD]
@@ -235,7 +208,7 @@ __global__ __launch_bounds__(256) void mha_tiled_bwd_dq_kernel(const TiledArgs a
 }
 
 template <int DP>
-__global__ __launch_bounds__(256) void mha_tiled_bwd_dkv_kernel(const TiledArgs a) {
+__global__ __launch_bounds__(256) void mha_tiled_bwd_dkv_kernel(const LseArgs a) {
     constexpr int LD = DP + 4, NT = DP / 16;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Ks = lds;                    // [64][LD]
@@ -319,42 +292,24 @@ __global__ __launch_bounds__(256) void mha_tiled_bwd_dkv_kernel(const TiledArgs 
 // The shapes the tiled pair runs: the single statement of its limits (r3d_mha_tiled_supported, and both launches).
 static bool tiled_shape_ok(int Lq, int Lk, int dh, bool /*bwd*/) { return Lq >= 1 && Lk >= 1 && dh >= 1 && dh <= 128; }
 
-static int tiled_dp(int dh) { return dh <= 16 ? 16 : dh <= 32 ? 32 : dh <= 64 ? 64 : 128; }
-
 static size_t tiled_lds_bytes(int dp, bool bwd) {
     return ((size_t)(bwd ? 4 : 3) * TT * (dp + 4) + (size_t)TT * SLD + (bwd ? 2 : 1) * TT) * sizeof(float);
 }
 
-static int tiled_check(const TiledArgs& a, bool bwd) {
-    if (!tiled_shape_ok(a.Lq, a.Lk, a.dh, bwd)) return R3D_EINVAL;
-    if (!a.q || !a.k || !a.v || !a.o || !a.lse) return R3D_EINVAL;
-    if (a.B <= 0 || a.heads <= 0 || a.B > 65535 || a.heads > 65535) return R3D_EINVAL;
-    const int H = a.heads * a.dh;
-    if (a.ldq < H || a.ldk < H || a.ldv < H || a.ldo < H) return R3D_EINVAL;
-    if (bwd && (!a.d_o || !a.delta || !a.dq || !a.dk || !a.dv || a.lddo < H || a.lddq < H || a.lddk < H || a.lddv < H))
-        return R3D_EINVAL;
-    return R3D_OK;
-}
-
 template <int DP>
-static int tiled_launch(const TiledArgs& a, bool bwd, hipStream_t s) {
+static int tiled_launch(const LseArgs& a, bool bwd, hipStream_t s) {
     const size_t lds = tiled_lds_bytes(DP, bwd);
     const dim3 gq(r3d_cdiv(a.Lq, TT), a.heads, a.B), gk(r3d_cdiv(a.Lk, TT), a.heads, a.B), blk(256);
     if (!bwd) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)mha_tiled_fwd_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
+        hipError_t e = allow_dynamic_lds((const void*)mha_tiled_fwd_kernel<DP>, lds);
+        if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL(mha_tiled_fwd_kernel<DP>, gq, blk, lds, s, a);
         R3D_LAUNCH_CHECK();
         return R3D_OK;
     }
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)mha_tiled_bwd_dq_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)mha_tiled_bwd_dkv_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = allow_dynamic_lds((const void*)mha_tiled_bwd_dq_kernel<DP>, lds);
+    if (e == hipSuccess) e = allow_dynamic_lds((const void*)mha_tiled_bwd_dkv_kernel<DP>, lds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(mha_tiled_bwd_dq_kernel<DP>, gq, blk, lds, s, a);       // writes delta ...
     R3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(mha_tiled_bwd_dkv_kernel<DP>, gk, blk, lds, s, a);      // ... which this one reads
@@ -362,11 +317,11 @@ static int tiled_launch(const TiledArgs& a, bool bwd, hipStream_t s) {
     return R3D_OK;
 }
 
-static int tiled_dispatch(const TiledArgs& a, bool bwd, void* stream) {
-    int rc = tiled_check(a, bwd);
+static int tiled_dispatch(LseArgs a, bool bwd, void* stream) {
+    int rc = lse_admit(a, tiled_shape_ok(a.Lq, a.Lk, a.dh, bwd), bwd, false);
     if (rc != R3D_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    switch (tiled_dp(a.dh)) {
+    switch (tile_dp(a.dh)) {
         case 16: return tiled_launch<16>(a, bwd, s);
         case 32: return tiled_launch<32>(a, bwd, s);
         case 64: return tiled_launch<64>(a, bwd, s);
@@ -384,12 +339,9 @@ R3D_EXPORT int r3d_mha_tiled_fwd(const float* q, int ldq, const float* k, int ld
                                  const uint8_t* key_padding_mask, const int64_t* key_label, int pad_idx,
                                  const uint8_t* drop_mask, float drop_scale, float* o, int ldo, float* lse, int B, int heads,
                                  int Lq, int Lk, int dh, void* stream) {
-    TiledArgs a{};
-    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.kpm = key_padding_mask;
-    a.key_label = key_label; a.pad_idx = pad_idx; a.drop = drop_mask; a.drop_scale = drop_scale;
-    a.o = o; a.ldo = ldo; a.lse = lse;
-    a.B = B; a.heads = heads; a.Lq = Lq; a.Lk = Lk; a.dh = dh; a.scale = dh > 0 ? 1.0f / sqrtf((float)dh) : 0.f;
-    return tiled_dispatch(a, false, stream);
+    return tiled_dispatch(lse_args(q, ldq, k, ldk, v, ldv, key_padding_mask, key_label, pad_idx, drop_mask, drop_scale, o, ldo, lse,
+                                   nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, B, heads, Lq, Lk, dh),
+                          false, stream);
 }
 
 R3D_EXPORT int r3d_mha_tiled_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
@@ -397,11 +349,7 @@ R3D_EXPORT int r3d_mha_tiled_bwd(const float* q, int ldq, const float* k, int ld
                                  const uint8_t* drop_mask, float drop_scale, const float* o, int ldo, const float* lse,
                                  const float* d_o, int lddo, float* delta, float* dq, int lddq, float* dk, int lddk, float* dv,
                                  int lddv, int B, int heads, int Lq, int Lk, int dh, void* stream) {
-    TiledArgs a{};
-    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.kpm = key_padding_mask;
-    a.key_label = key_label; a.pad_idx = pad_idx; a.drop = drop_mask; a.drop_scale = drop_scale;
-    a.o = const_cast<float*>(o); a.ldo = ldo; a.lse = const_cast<float*>(lse); a.d_o = d_o; a.lddo = lddo; a.delta = delta;
-    a.dq = dq; a.lddq = lddq; a.dk = dk; a.lddk = lddk; a.dv = dv; a.lddv = lddv;
-    a.B = B; a.heads = heads; a.Lq = Lq; a.Lk = Lk; a.dh = dh; a.scale = dh > 0 ? 1.0f / sqrtf((float)dh) : 0.f;
-    return tiled_dispatch(a, true, stream);
+    return tiled_dispatch(lse_args(q, ldq, k, ldk, v, ldv, key_padding_mask, key_label, pad_idx, drop_mask, drop_scale, o, ldo, lse,
+                                   d_o, lddo, delta, dq, lddq, dk, lddk, dv, lddv, nullptr, B, heads, Lq, Lk, dh),
+                          true, stream);
 }

@@ -202,15 +202,11 @@ __global__ __launch_bounds__(256) void cnn_seg_step_kernel(const r3d_cnn_seg_arg
 // The shapes the kernel runs: the single statement of its limit (r3d_cnn_seg_supported, and the launch).
 static bool cnn_shape_ok(int H, int Kseg) { return H >= 8 && H % 4 == 0 && H <= kCnnMaxH && Kseg >= 1 && Kseg <= kCnnMaxK; }
 
-static int cnn_dp(int H) { return H <= 16 ? 16 : H <= 32 ? 32 : H <= 64 ? 64 : H <= 128 ? 128 : 256; }
-
 template <int DP>
 static int cnn_launch(const r3d_cnn_seg_args& a, float* ws, hipStream_t s) {
     const size_t lds = cnn_lds_bytes(DP);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)cnn_seg_step_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = allow_dynamic_lds((const void*)cnn_seg_step_kernel<DP>, lds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(cnn_seg_step_kernel<DP>, dim3(r3d_cdiv(a.N, TT)), dim3(256), lds, s, a, ws);
     R3D_LAUNCH_CHECK();
     return R3D_OK;
@@ -237,7 +233,7 @@ R3D_EXPORT int r3d_cnn_seg_step(const r3d_cnn_seg_args* p, float* ws, void* stre
         (a.d_extra && a.ld_dextra % 4))
         return R3D_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    switch (cnn_dp(a.H)) {
+    switch (tile_dp(a.H)) {
         case 16: return cnn_launch<16>(a, ws, s);
         case 32: return cnn_launch<32>(a, ws, s);
         case 64: return cnn_launch<64>(a, ws, s);

@@ -563,8 +563,6 @@ __global__ __launch_bounds__(256) void supcon_wide_rows_kernel(const SupconArgs 
 // The widths the pair runs: the single statement of its limit (r3d_supcon_supported, and both launches).
 static bool supcon_width_ok(int D) { return D >= 1 && D <= SUPCON_MAX_D; }
 
-static int supcon_dp(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : D <= 128 ? 128 : 256; }
-
 static bool supcon_wide_width_ok(int D) { return D >= 1 && D <= SUPCON_WIDE_MAX_D; }
 
 static int supcon_check(const SupconArgs& a, bool bwd, bool wide = false) {
@@ -580,11 +578,8 @@ template <int DP>
 static int supcon_launch(const SupconArgs& a, bool bwd, hipStream_t s) {
     const size_t lds = supcon_lds_bytes(DP);
     const dim3 grid(r3d_cdiv(a.N, TT)), blk(256);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(bwd ? (const void*)supcon_bwd_kernel<DP> : (const void*)supcon_fwd_kernel<DP>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = allow_dynamic_lds(bwd ? (const void*)supcon_bwd_kernel<DP> : (const void*)supcon_fwd_kernel<DP>, lds);
+    if (e != hipSuccess) return (int)e;
     if (bwd) {
         hipLaunchKernelGGL(supcon_bwd_kernel<DP>, grid, blk, lds, s, a);
         R3D_LAUNCH_CHECK();
@@ -601,7 +596,7 @@ static int supcon_dispatch(const SupconArgs& a, bool bwd, void* stream) {
     int rc = supcon_check(a, bwd);
     if (rc != R3D_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    switch (supcon_dp(a.D)) {
+    switch (tile_dp(a.D)) {
         case 16: return supcon_launch<16>(a, bwd, s);
         case 32: return supcon_launch<32>(a, bwd, s);
         case 64: return supcon_launch<64>(a, bwd, s);

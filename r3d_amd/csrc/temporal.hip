@@ -552,8 +552,6 @@ __global__ __launch_bounds__(256) void tcon_bwd_kernel(const TconArgs a) {
     }
 }
 
-static int tcon_dp(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : D <= 128 ? 128 : 256; }
-
 static int tcon_check(const TconArgs& a, bool bwd) {
     if (!temporal_width_ok(a.D) || !temporal_rows_ok(a.B, a.T)) return R3D_EINVAL;
     if (!a.x || !a.ws || a.ld < a.D || !a.first || !a.last) return R3D_EINVAL;
@@ -567,11 +565,8 @@ template <int DP>
 static int tcon_launch(const TconArgs& a, bool bwd, hipStream_t s) {
     const size_t lds = tcon_lds_bytes(DP);
     const dim3 grid(r3d_cdiv(a.T, TT), a.B), blk(256);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(bwd ? (const void*)tcon_bwd_kernel<DP> : (const void*)tcon_fwd_kernel<DP>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = allow_dynamic_lds(bwd ? (const void*)tcon_bwd_kernel<DP> : (const void*)tcon_fwd_kernel<DP>, lds);
+    if (e != hipSuccess) return (int)e;
     if (bwd) {
         hipLaunchKernelGGL(tcon_bwd_kernel<DP>, grid, blk, lds, s, a);
         R3D_LAUNCH_CHECK();
@@ -588,7 +583,7 @@ static int tcon_dispatch(const TconArgs& a, bool bwd, void* stream) {
     int rc = tcon_check(a, bwd);
     if (rc != R3D_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    switch (tcon_dp(a.D)) {
+    switch (tile_dp(a.D)) {
         case 16: return tcon_launch<16>(a, bwd, s);
         case 32: return tcon_launch<32>(a, bwd, s);
         case 64: return tcon_launch<64>(a, bwd, s);

@@ -1,5 +1,5 @@
-// The 64 x 64 tile discipline shared by the tiled attention core (attention_tiled.hip) and the supervised contrastive
-// loss (supcon.hip): 256 threads = 4 waves, operand tiles of 64 rows staged in LDS with the width zero-padded to DP and
+// The 64 x 64 tile discipline shared by the tiled and split-key attention cores (attention_tiled.hip,
+// attention_splitk.hip), the contrastive losses (supcon.hip, temporal.hip) and the CNN's head (cnn.hip): 256 threads = 4 waves, operand tiles of 64 rows staged in LDS with the width zero-padded to DP and
 // a row stride of DP + 4 floats, score tiles of 64 x 64 with a row stride of 68.  Wave w owns rows [16w, 16w + 16) of
 // a tile; every product is a chain of fp32-input 16x16x4 MFMAs on LDS operands (exact fp32, one VGPR per operand).
 // Each lane feeds FOUR k-steps from one 16-byte LDS read: step t of lane (c, kq) carries k = k0 + 4 kq + t on both
@@ -77,6 +77,16 @@ __device__ __forceinline__ float quad_sum(float v) {       // over the 4 lanes o
     v += __shfl_xor(v, 1);
     v += __shfl_xor(v, 2);
     return v;
+}
+
+// ---- host side of every user ------------------------------------------------------------------------------------------
+// the padded width DP of the instance that runs a head / row width (each user's own check caps the width)
+static inline int tile_dp(int width) { return width <= 16 ? 16 : width <= 32 ? 32 : width <= 64 ? 64 : width <= 128 ? 128 : 256; }
+
+// a kernel launched with more than 64 KiB of dynamic LDS has to opt in (per device, so at every call); the HIP error
+static inline hipError_t allow_dynamic_lds(const void* kernel, size_t bytes) {
+    if (bytes <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 }  // namespace r3d

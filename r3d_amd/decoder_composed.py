@@ -9,11 +9,11 @@ One decoder serves the three: `rows` query rows (B clips x Tq queries) attend to
   g_qpos       where the query position's gradient goes -- None: added into w.d_qpos through w.d_qtmp (an activation: it flows
                on into the engine's branch); a parameter's gradient tensor: folded over the clips with rowmod_sum;
   mem          the memory (w.mem or w.fused);
-  w.route      "core" (r3d_mha_core_*, the probabilities kept) or "tiled" (r3d_mha_tiled_*, lse kept, probabilities recomputed).
+  w.route      the route of both attentions (r3d_amd/attention.py).
 Kernels are called as attributes of the ops module: the tests patch them there and count the calls."""
 import torch
 
-from . import ops
+from . import attention, ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
 from .engine_base import DROP_P
 
@@ -49,11 +49,9 @@ def decoder_buffers(w, eng, Tq, route, train, own_drop_sizes):
     R = B * Tq
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)     # noqa: E731
     w.route = route
-    if route == "tiled":                  # no [B, heads, Tq, S] probabilities: lse per attention, one delta workspace
-        att = lambda: dict(lse_sa=f(B, heads, Tq), lse_ca=f(B, heads, Tq))        # noqa: E731
-        w.delta = f(B, heads, Tq) if train else None
-    else:
-        att = lambda: dict(p_sa=f(B, heads, Tq, Tq), p_ca=f(B, heads, Tq, S))      # noqa: E731
+    att = lambda: {**attention.saved(route, "sa", f, B, heads, Tq, Tq, H // heads, train),        # noqa: E731
+                   **attention.saved(route, "ca", f, B, heads, Tq, S, H // heads, train)}
+    w.delta = attention.delta_buffer(route, f, B, heads, Tq, train)
     w.tgt0 = torch.zeros(R, H, dtype=torch.float32, device=dev)           # tgt = zeros_like(query)
     w.layers = [dict(sa_qkv=f(R, 3 * H), sa_o=f(R, H), t1_pre=f(R, H), t1=f(R, H), m1=f(R), r1=f(R), caq=f(R, H),
                      cakv=f(N, 2 * H), ca_o=f(R, H), t2_pre=f(R, H), t2=f(R, H), m2=f(R), r2=f(R), ff1=f(R, 4 * H),
@@ -78,14 +76,6 @@ def decoder_forward(eng, w, qpos, qmod, mem, key_labels, drop):
     dm2 = lambda k, cols: eng._dm2(dm(k), R, cols)         # noqa: E731
     dsc = DROP_SCALE
 
-    def attend(q, k, v, c, at, Lk, l, **mask):
-        if w.route == "tiled":
-            ops.mha_tiled_fwd(q, k, v, c[at + "_o"], c["lse_" + at], B, heads, Tq, Lk, dh, drop_mask=dm(f"{at}_p{l}"),
-                              drop_scale=dsc, **mask)
-        else:
-            ops.mha_core_fwd(q, k, v, c["p_" + at], c[at + "_o"], B, heads, Tq, Lk, dh, drop_mask=dm(f"{at}_p{l}"),
-                             drop_scale=dsc, **mask)
-
     pos = a.p("pos_embedding")[0, :S]
     tgt = w.tgt0
     for l in range(eng.L):
@@ -93,14 +83,15 @@ def decoder_forward(eng, w, qpos, qmod, mem, key_labels, drop):
         p = lambda n: a.p(pl + n)         # noqa: E731
         ops.gemm(GEMM_NT, tgt, p("self_attn.in_proj_weight"), c["sa_qkv"], a_add=qpos, a_add_mod=qmod,
                  bias=p("self_attn.in_proj_bias"), ws=ws)
-        attend(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c, "sa", Tq, l)
+        attention.forward(w.route, "sa", c, *attention.thirds(c["sa_qkv"]), (B, heads, Tq, Tq, dh), dm(f"sa_p{l}"), dsc)
         ops.gemm(GEMM_NT, c["sa_o"], p("self_attn.out_proj.weight"), c["t1_pre"], bias=p("self_attn.out_proj.bias"),
                  drop_mask=dm2(f"d1_{l}", H), drop_scale=dsc, res1=None if l == 0 else tgt, ws=ws)
         ops.layernorm_fwd(c["t1_pre"], p("norm1.weight"), p("norm1.bias"), c["t1"], c["m1"], c["r1"])
         wi, bi = p("multihead_attn.in_proj_weight"), p("multihead_attn.in_proj_bias")
         ops.gemm(GEMM_NT, c["t1"], wi[:H], c["caq"], a_add=qpos, a_add_mod=qmod, bias=bi[:H], ws=ws)
         ops.gemm(GEMM_NT, mem, wi[H:], c["cakv"], a_add=pos, a_add_mod=S, bias=bi[H:], ws=ws)
-        attend(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c, "ca", S, l, key_labels=key_labels, pad_idx=eng.pad_idx)
+        attention.forward(w.route, "ca", c, c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], (B, heads, Tq, S, dh), dm(f"ca_p{l}"),
+                          dsc, key_labels=key_labels, pad_idx=eng.pad_idx)
         ops.gemm(GEMM_NT, c["ca_o"], p("multihead_attn.out_proj.weight"), c["t2_pre"],
                  bias=p("multihead_attn.out_proj.bias"), drop_mask=dm2(f"d2_{l}", H), drop_scale=dsc, res1=c["t1"], ws=ws)
         ops.layernorm_fwd(c["t2_pre"], p("norm2.weight"), p("norm2.bias"), c["t2"], c["m2"], c["r2"])
@@ -131,14 +122,6 @@ def decoder_backward(eng, w, qpos, qmod, mem, key_labels, drop, g_qpos=None):
     def wgrad(dy, x, gw, gb, **kw):
         ops.gemm(GEMM_TN, dy, x, gw, bias_grad=gb, ws=ws, **kw)
 
-    def attend_bwd(q, k, v, c, at, d_o, dq, dk, dv, Lk, l, **mask):
-        if w.route == "tiled":            # (the probabilities are recomputed: the forward's key mask again)
-            ops.mha_tiled_bwd(q, k, v, c[at + "_o"], c["lse_" + at], d_o, w.delta, dq, dk, dv, B, heads, Tq, Lk, dh,
-                              drop_mask=dmf(f"{at}_p{l}"), drop_scale=dsc, **mask)
-        else:
-            ops.mha_core_bwd(q, k, v, c["p_" + at], d_o, dq, dk, dv, B, heads, Tq, Lk, dh, drop_mask=dmf(f"{at}_p{l}"),
-                             drop_scale=dsc)
-
     ln_bwd(w.d_tgtF, w.layers[-1]["t3"], w.mF, w.rF, "transformer.decoder.norm", w.d_t)
     dy, dy2 = w.d_t, None
     for l in reversed(range(L)):
@@ -157,8 +140,9 @@ def decoder_backward(eng, w, qpos, qmod, mem, key_labels, drop, g_qpos=None):
                drop_mask=dm(f"d2_{l}", H), drop_scale=dsc)
         wgrad(gl["cap"], c["ca_o"], g("multihead_attn.out_proj.weight"), g("multihead_attn.out_proj.bias"))
         ops.gemm(GEMM_NN, gl["cap"], p("multihead_attn.out_proj.weight"), gl["cao"], ws=ws)
-        attend_bwd(c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], c, "ca", gl["cao"], gl["caq"], gl["cakv"][:, :H],
-                   gl["cakv"][:, H:], S, l, key_labels=key_labels, pad_idx=eng.pad_idx)
+        attention.backward(w.route, "ca", c, c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], gl["cao"], gl["caq"],
+                           gl["cakv"][:, :H], gl["cakv"][:, H:], w.delta, (B, heads, Tq, S, dh), dmf(f"ca_p{l}"), dsc,
+                           key_labels=key_labels, pad_idx=eng.pad_idx)
         wi = p("multihead_attn.in_proj_weight")
         gwi, gbi = g("multihead_attn.in_proj_weight"), g("multihead_attn.in_proj_bias")
         wgrad(gl["cakv"], mem, gwi[H:], gbi[H:], b_add=pos, b_add_mod=S)
@@ -169,8 +153,8 @@ def decoder_backward(eng, w, qpos, qmod, mem, key_labels, drop, g_qpos=None):
                drop_mask=dm(f"d1_{l}", H), drop_scale=dsc)
         wgrad(gl["sap"], c["sa_o"], g("self_attn.out_proj.weight"), g("self_attn.out_proj.bias"))
         ops.gemm(GEMM_NN, gl["sap"], p("self_attn.out_proj.weight"), gl["sao"], ws=ws)
-        attend_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c, "sa", gl["sao"],
-                   gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], Tq, l)
+        attention.backward(w.route, "sa", c, *attention.thirds(c["sa_qkv"]), gl["sao"], *attention.thirds(gl["saqkv"]),
+                           w.delta, (B, heads, Tq, Tq, dh), dmf(f"sa_p{l}"), dsc)
         wgrad(gl["saqkv"], tgt_in, g("self_attn.in_proj_weight"), g("self_attn.in_proj_bias"), b_add=qpos, b_add_mod=qmod)
         ops.gemm(GEMM_NN, gl["saqkv"], p("self_attn.in_proj_weight"), gl["sain"], ws=ws)      # d (tgt_in + query_pos)
         # d query_pos += caqin + sain, top layer first

@@ -18,7 +18,7 @@ import math
 
 import torch
 
-from . import ops
+from . import attention, ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
 from .decoder_composed import decoder_drop_sizes, drop_pool
 from .engine_base import DROP_P, EXCLUDE_CLASS_IDX, EngineBase, ParamArena          # noqa: F401  (re-exported)
@@ -91,22 +91,14 @@ def check_engine_shape(H, heads, Q, bn=False, vary=False, plain=False):
                          f"n_query * head width <= 1024 outputs per wave")
 
 
-CROSS_ROUTES = ("core", "splitk", "tiled")
+CROSS_ROUTES = attention.ROUTES
 
 
 def cross_attention_route(Q, S, dh, train, long_clips):
-    """The kernels the decoder's cross-attention (Q queries against the S frames of a clip) runs through: "core"
-    (r3d_mha_core_*, wherever it admits the shape -- so a clip it admits launches the same kernels whatever the flag, as
-    engine_unsup.query_attention_route), past it and only with long_clips (opts --long_clips, read by the models into
-    r3d_long_clips) "splitk" (r3d_mha_splitk_*, csrc/attention_splitk.hip: Q <= 16) or "tiled" (r3d_mha_tiled_* with
-    Lq = Q: more queries), or None (refused)."""
-    if ops.mha_core_supported(Q, S, dh, train):
-        return "core"
-    if long_clips and ops.mha_splitk_supported(Q, S, dh, train):
-        return "splitk"
-    if long_clips and ops.mha_tiled_supported(Q, S, dh, train):
-        return "tiled"
-    return None
+    """The route (attention.pick) of the decoder's cross-attention, Q queries against the S frames of a clip: "core", past it
+    and only with long_clips (opts --long_clips, read by the models into r3d_long_clips) "splitk" (Q <= 16) or "tiled", or
+    None (refused)."""
+    return attention.pick(Q, S, dh, train, CROSS_ROUTES if long_clips else CROSS_ROUTES[:1])
 
 
 def cross_route_supported(route, Q, S, dh, train):
@@ -125,9 +117,7 @@ def check_clip_shape(S, H, heads, Q, max_pos_len, train, long_clips=False):
         raise ValueError(f"clip length {S} > max_pos_len {max_pos_len}: the rows of pos_embedding")
     dh = H // heads
     if cross_attention_route(Q, S, dh, train, long_clips) is None:
-        hint, flagged = "", None if long_clips else cross_attention_route(Q, S, dh, train, True)
-        if flagged is not None:
-            hint = f" (the {'split-key' if flagged == 'splitk' else 'tiled'} core runs this shape: --long_clips)"
+        hint = "" if long_clips else attention.long_clips_hint(Q, S, dh, train, CROSS_ROUTES)
         raise ValueError(f"clip length {S} at head width {dh}: the cross-attention core's {'backward' if train else 'forward'} "
                          f"keeps {Q} x {S} scores in LDS, past its 160 KiB" + hint)
 
@@ -157,14 +147,7 @@ def check_erank_shape(B, S, H, route="jacobi"):
 
 def max_clip_len(H, heads, Q, max_pos_len, train, long_clips=False):
     """The longest clip check_clip_shape admits (the LDS bound grows monotonically with S)."""
-    lo, hi = 0, max_pos_len
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if cross_attention_route(Q, mid, H // heads, train, long_clips) is not None:
-            lo = mid
-        else:
-            hi = mid - 1
-    return lo
+    return attention.longest(lambda S: cross_attention_route(Q, S, H // heads, train, long_clips) is not None, max_pos_len)
 
 
 class _Shape:
@@ -190,26 +173,17 @@ class _Shape:
         self.m1, self.r1, self.m2, self.r2, self.mf, self.rf = f(2 * N), f(2 * N), f(2 * N), f(2 * N), f(2 * N), f(2 * N)
         self.fused = f(N, H)
         self.tgt0 = torch.zeros(BQ, H, dtype=torch.float32, device=dev)
-        # the cross-attention's route (cross_attention_route): past the core no [B, heads, Q, S] probabilities are kept --
-        # lse per layer, one delta, and on the split-key route its chunk partials (forward and backward share them)
+        # the cross-attention's route (cross_attention_route) decides what its site keeps; the self-attention runs on the core
         self.route = eng._cross_route(S, train)
         dh = H // heads
-        self.layers = []
-        for _ in range(L):
-            d = dict(sa_qkv=f(BQ, 3 * H), sa_o=f(BQ, H), p_sa=f(B, heads, Q, Q), t1_pre=f(BQ, H),
-                     t1=f(BQ, H), m1=f(BQ), r1=f(BQ), caq=f(BQ, H), cakv=f(N, 2 * H), ca_o=f(BQ, H),
-                     t2_pre=f(BQ, H), t2=f(BQ, H), m2=f(BQ), r2=f(BQ), ff1=f(BQ, 4 * H),
-                     t3_pre=f(BQ, H), t3=f(BQ, H), m3=f(BQ), r3=f(BQ))
-            if self.route == "core":
-                d["p_ca"] = f(B, heads, Q, S)
-            else:
-                d["lse_ca"] = f(B, heads, Q)
-            if self.route == "splitk":
-                d["ws_ca"] = f(max(ops.mha_splitk_ws_floats(B, heads, Q, S, dh, False),
-                                   ops.mha_splitk_ws_floats(B, heads, Q, S, dh, True) if train else 0))
-            self.layers.append(d)
-        if self.route != "core" and train:
-            self.delta = f(B, heads, Q)
+        self.layers = [dict(sa_qkv=f(BQ, 3 * H), sa_o=f(BQ, H), p_sa=f(B, heads, Q, Q), t1_pre=f(BQ, H),
+                            t1=f(BQ, H), m1=f(BQ), r1=f(BQ), caq=f(BQ, H), cakv=f(N, 2 * H), ca_o=f(BQ, H),
+                            t2_pre=f(BQ, H), t2=f(BQ, H), m2=f(BQ), r2=f(BQ), ff1=f(BQ, 4 * H),
+                            t3_pre=f(BQ, H), t3=f(BQ, H), m3=f(BQ), r3=f(BQ),
+                            **attention.saved(self.route, "ca", f, B, heads, Q, S, dh, train)) for _ in range(L)]
+        delta = attention.delta_buffer(self.route, f, B, heads, Q, train)
+        if delta is not None:
+            self.delta = delta
         self.tgtF, self.mF, self.rF = f(BQ, H), f(BQ), f(BQ)
         self.actdur = f(BQ, K + 1)
         self.seg = f(N, K)
@@ -531,8 +505,8 @@ class FusionEngine(EngineBase):
             c, pl = w.layers[l], f"transformer.decoder.layers.{l}."
             ops.gemm(GEMM_NT, tgt_in, a.p(pl + "self_attn.in_proj_weight"), c["sa_qkv"], a_add=qpos, a_add_mod=Q,
                      bias=a.p(pl + "self_attn.in_proj_bias"), ws=wsx)
-            ops.mha_core_fwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], c["sa_o"], B,
-                             heads, Q, Q, dh, drop_mask=dm(f"sa_p{l}"), drop_scale=dsc)
+            ops.mha_core_fwd(*attention.thirds(c["sa_qkv"]), c["p_sa"], c["sa_o"], B, heads, Q, Q, dh, drop_mask=dm(f"sa_p{l}"),
+                             drop_scale=dsc)
             if self._gln(BQ, H):
                 ops.gemm_ln_fwd([dict(a=c["sa_o"], w=a.p(pl + "self_attn.out_proj.weight"),
                                       bias=a.p(pl + "self_attn.out_proj.bias"), drop_mask=self._dm2(dm(f"d1_{l}"), BQ, H),
@@ -927,8 +901,9 @@ class FusionEngine(EngineBase):
         g1, g2, g3 = w.tables[key]
         g1.launch()
         gln = self._gln(2 * w.N, H) and self._gln(2 * w.N, 4 * H) and self._gln(BQ, 0)
-        sa = dict(q=c["sa_qkv"][:, :H], k=c["sa_qkv"][:, H:2 * H], v=c["sa_qkv"][:, 2 * H:], probs=c["p_sa"], o=c["sa_o"], B=B,
-                  heads=heads, Lq=Q, Lk=Q, dh=dh, drop_mask=dm("sa_p0"), drop_scale=dsc)
+        q, k, v = attention.thirds(c["sa_qkv"])
+        sa = dict(q=q, k=k, v=v, probs=c["p_sa"], o=c["sa_o"], B=B, heads=heads, Lq=Q, Lk=Q, dh=dh, drop_mask=dm("sa_p0"),
+                  drop_scale=dsc)
         ride = gln and self.ride_attention and ops.gemm_ln_mha_supported(heads, Q, Q, dh)
         if gln:      # attn.proj + x -> norm2 (transformerblock.py:131-132): the LayerNorm is the product's epilogue; the
             #          query self-attention core (parameters only) rides in the same launch
@@ -961,32 +936,6 @@ class FusionEngine(EngineBase):
                      pair_out=w.fused)])
         self._erank_fork(w)
         g3.launch()
-
-    def _cross_fwd(self, w, c, key_labels, drop_mask, dsc):
-        """The cross-attention core of one decoder layer on the workspace's route (cross_attention_route)."""
-        H, args = self.H, (w.B, self.heads, self.Q, w.S, self.dh)
-        q, k, v = c["caq"], c["cakv"][:, :H], c["cakv"][:, H:]
-        kw = dict(key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=drop_mask, drop_scale=dsc)
-        if w.route == "core":
-            ops.mha_core_fwd(q, k, v, c["p_ca"], c["ca_o"], *args, **kw)
-        elif w.route == "splitk":
-            ops.mha_splitk_fwd(q, k, v, c["ca_o"], c["lse_ca"], c["ws_ca"], *args, **kw)
-        else:
-            ops.mha_tiled_fwd(q, k, v, c["ca_o"], c["lse_ca"], *args, **kw)
-
-    def _cross_bwd(self, w, c, gl, key_labels, drop_mask, dsc):
-        """Its adjoint: past the core the probabilities are recomputed, so the forward's key labels are passed again."""
-        H, args = self.H, (w.B, self.heads, self.Q, w.S, self.dh)
-        q, k, v = c["caq"], c["cakv"][:, :H], c["cakv"][:, H:]
-        dq, dk, dv = gl["caq"], gl["cakv"][:, :H], gl["cakv"][:, H:]
-        if w.route == "core":
-            ops.mha_core_bwd(q, k, v, c["p_ca"], gl["cao"], dq, dk, dv, *args, drop_mask=drop_mask, drop_scale=dsc)
-            return
-        kw = dict(key_labels=key_labels, pad_idx=self.pad_idx, drop_mask=drop_mask, drop_scale=dsc)
-        if w.route == "splitk":
-            ops.mha_splitk_bwd(q, k, v, c["ca_o"], c["lse_ca"], gl["cao"], w.delta, dq, dk, dv, c["ws_ca"], *args, **kw)
-        else:
-            ops.mha_tiled_bwd(q, k, v, c["ca_o"], c["lse_ca"], gl["cao"], w.delta, dq, dk, dv, *args, **kw)
 
     def _decoder_unfused(self, w, key_labels, dm, dsc, multi, main, s2, sa_block, paired=False):
         """The decoder composed from the GEMM / attention / LayerNorm entry points (any shape)."""
@@ -1028,7 +977,8 @@ class FusionEngine(EngineBase):
                 ops.layernorm_fwd(c["t3_pre"], a.p(pl + "norm3.weight"), a.p(pl + "norm3.bias"), c["t3"], c["m3"], c["r3"])
                 tgt = c["t3"]
                 continue
-            self._cross_fwd(w, c, key_labels, dm(f"ca_p{l}"), dsc)
+            attention.forward(w.route, "ca", c, c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], (B, heads, Q, S, dh),
+                              dm(f"ca_p{l}"), dsc, key_labels=key_labels, pad_idx=self.pad_idx)
             if self._gln(BQ, H):      # out_proj -> dropout -> + tgt -> norm2 (transformer.py:304-306): one launch
                 ops.gemm_ln_fwd([dict(a=c["ca_o"], w=a.p(pl + "multihead_attn.out_proj.weight"),
                                       bias=a.p(pl + "multihead_attn.out_proj.bias"),
@@ -1455,7 +1405,9 @@ class FusionEngine(EngineBase):
             ln_bwd(f"d2_{l}", gl["t2"], c["t2_pre"], c["m2"], c["r2"], pl + "norm2.weight", pl + "norm2.bias", gl["t2pre"],
                    dy2=gl["t2b"] if split else None, dx2=gl["cap"], drop_mask=dm(f"d2_{l}", BQ, H), drop_scale=dsc)
             ops.gemm(GEMM_NN, gl["cap"], p("multihead_attn.out_proj.weight"), gl["cao"], ws=ws)
-            self._cross_bwd(w, c, gl, st["key_labels"], dmf(f"ca_p{l}"), dsc)
+            attention.backward(w.route, "ca", c, c["caq"], c["cakv"][:, :H], c["cakv"][:, H:], gl["cao"], gl["caq"],
+                               gl["cakv"][:, :H], gl["cakv"][:, H:], getattr(w, "delta", None), (B, heads, Q, S, dh),
+                               dmf(f"ca_p{l}"), dsc, key_labels=st["key_labels"], pad_idx=self.pad_idx)
             wi = p("multihead_attn.in_proj_weight")
             if st.get("paired"):
                 break                          # one layer, one stream: continued below with paired launches
@@ -1469,9 +1421,8 @@ class FusionEngine(EngineBase):
                 ln_bwd(f"d1_{l}", gl["caqin"], c["t1_pre"], c["m1"], c["r1"], pl + "norm1.weight", pl + "norm1.bias",
                        gl["t1pre"], dy2=gl["t2pre"], dx2=gl["sap"], drop_mask=dm(f"d1_{l}", BQ, H), drop_scale=dsc)
                 ops.gemm(GEMM_NN, gl["sap"], p("self_attn.out_proj.weight"), gl["sao"], ws=ws2)
-                ops.mha_core_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], gl["sao"],
-                                 gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], B, heads, Q, Q, dh,
-                                 drop_mask=dmf(f"sa_p{l}"), drop_scale=dsc)
+                ops.mha_core_bwd(*attention.thirds(c["sa_qkv"]), c["p_sa"], gl["sao"], *attention.thirds(gl["saqkv"]), B, heads,
+                                 Q, Q, dh, drop_mask=dmf(f"sa_p{l}"), drop_scale=dsc)
                 ops.gemm(GEMM_NN, gl["saqkv"], p("self_attn.in_proj_weight"), gl["sain"], ws=ws2)
             ops.gemm(GEMM_NN, gl["cakv"], wi[H:], w.d_fused, accumulate=not first_fused, ws=ws)   # d (memory + pos)
             first_fused = False
@@ -1581,9 +1532,8 @@ class FusionEngine(EngineBase):
             if ride_bwd:
                 w.tables[("bwd_ride",)][0].launch()                  # d_u -> d_h2 alone; the attention core follows below
             else:
-                ops.mha_core_bwd(c["sa_qkv"][:, :H], c["sa_qkv"][:, H:2 * H], c["sa_qkv"][:, 2 * H:], c["p_sa"], gl["sao"],
-                                 gl["saqkv"][:, :H], gl["saqkv"][:, H:2 * H], gl["saqkv"][:, 2 * H:], B, heads, Q, Q, dh,
-                                 drop_mask=dmf("sa_p0"), drop_scale=dsc)
+                ops.mha_core_bwd(*attention.thirds(c["sa_qkv"]), c["p_sa"], gl["sao"], *attention.thirds(gl["saqkv"]), B, heads,
+                                 Q, Q, dh, drop_mask=dmf("sa_p0"), drop_scale=dsc)
                 gb3.launch()
         else:
             if st.get("erank"):
@@ -1599,13 +1549,13 @@ class FusionEngine(EngineBase):
             pass
         elif ride_bwd:
             c0, gl0 = w.layers[0], w.glayers[0]
+            (q, k, v), (dq, dk, dv) = attention.thirds(c0["sa_qkv"]), attention.thirds(gl0["saqkv"])
             ops.layernorm_bwd_multi(
                 [dict(dy=w.d_h2, x=w.x1, mean=w.m2, rstd=w.r2, gamma=a.p(pre + "norm2.weight"), beta=a.p(pre + "norm2.bias"),
                       dx=w.d_x1, dgamma=a.g(pre + "norm2.weight"), dbeta=a.g(pre + "norm2.bias"), partial=w.lnp["n2"],
                       add1=w.d_x3)],
-                mha=dict(q=c0["sa_qkv"][:, :H], k=c0["sa_qkv"][:, H:2 * H], v=c0["sa_qkv"][:, 2 * H:], probs=c0["p_sa"],
-                         d_o=gl0["sao"], dq=gl0["saqkv"][:, :H], dk=gl0["saqkv"][:, H:2 * H], dv=gl0["saqkv"][:, 2 * H:], B=B,
-                         heads=heads, Lq=Q, Lk=Q, dh=dh, drop_mask=dmf("sa_p0"), drop_scale=dsc))
+                mha=dict(q=q, k=k, v=v, probs=c0["p_sa"], d_o=gl0["sao"], dq=dq, dk=dk, dv=dv, B=B, heads=heads, Lq=Q, Lk=Q,
+                         dh=dh, drop_mask=dmf("sa_p0"), drop_scale=dsc))
             w.tables[("bwd_ride",)][1].launch()
         else:
             ln_bwd("n2", w.d_h2, w.x1, w.m2, w.r2, pre + "norm2.weight", pre + "norm2.bias", w.d_x1, add1=w.d_x3,

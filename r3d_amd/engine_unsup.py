@@ -15,7 +15,7 @@ seam / tail fusions): it is a coverage row of SURVEY.md 8(a) A2/A3, not the head
 """
 import torch
 
-from . import ops
+from . import attention, ops
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN
 from .decoder_composed import DROP_SCALE, decoder_buffers, decoder_forward, decoder_backward
 from .engine import check_hidden
@@ -26,16 +26,13 @@ from .engine_base import DROP_P, EXCLUDE_CLASS_IDX, EngineBase
 # limits (S * head width <= 1024 outputs per wave, S x S scores in 160 KiB of LDS) bound the clip length itself.  Checked on
 # the host before anything is enqueued; tests/test_query_admission_cpu.py pins them.  long_clips (opts --long_clips, read by
 # the models into r3d_long_clips) adds the tiled core (csrc/attention_tiled.hip) for the shapes past those limits.
+QUERY_ROUTES = ("core", "tiled")        # (never "splitk": S queries)
+
+
 def query_attention_route(S, H, heads, train, long_clips):
-    """The attention kernels both decoder attentions of an S-frame clip run through: "core" (r3d_mha_core_*, wherever it
-    admits the shape -- so a short clip launches the same kernels whatever the flag), "tiled" (r3d_mha_tiled_*, only with
-    long_clips) or None (refused)."""
-    dh = H // heads
-    if ops.mha_core_supported(S, S, dh, train):
-        return "core"
-    if long_clips and ops.mha_tiled_supported(S, S, dh, train):
-        return "tiled"
-    return None
+    """The route (attention.pick) of both decoder attentions of an S-frame clip: "core", "tiled" (only with long_clips) or
+    None (refused)."""
+    return attention.pick(S, S, H // heads, train, QUERY_ROUTES if long_clips else QUERY_ROUTES[:1])
 
 
 def check_query_engine_shape(H, heads, long_clips=False):
@@ -56,9 +53,7 @@ def check_query_clip_shape(S, H, heads, max_pos_len, train, long_clips=False):
         raise ValueError(f"clip length {S} > max_pos_len {max_pos_len}: the rows of the positional tables")
     dh = H // heads
     if query_attention_route(S, H, heads, train, long_clips) is None:
-        hint = ""
-        if not long_clips and ops.mha_tiled_supported(S, S, dh, train):
-            hint = " (the tiled core runs this shape: --long_clips)"
+        hint = "" if long_clips else attention.long_clips_hint(S, S, dh, train, QUERY_ROUTES)
         raise ValueError(f"clip length {S} at head width {dh}: the decoder's attention cores run {S} queries x {S} keys, past "
                          f"the {'backward' if train else 'forward'} core's S * head width <= 1024 outputs per wave or its "
                          f"S x S scores in 160 KiB of LDS" + hint)
@@ -66,14 +61,7 @@ def check_query_clip_shape(S, H, heads, max_pos_len, train, long_clips=False):
 
 def max_query_clip_len(H, heads, max_pos_len, train, long_clips=False):
     """The longest clip check_query_clip_shape admits (0: none; the bound tightens monotonically with S)."""
-    lo, hi = 0, max_pos_len
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if query_attention_route(mid, H, heads, train, long_clips) is not None:
-            lo = mid
-        else:
-            hi = mid - 1
-    return lo
+    return attention.longest(lambda S: query_attention_route(S, H, heads, train, long_clips) is not None, max_pos_len)
 
 
 LIVE_PREFIXES = ("input_embed.", "depth_projection.", "depth_layernorm.", "pos_embedding", "transformer.decoder.",
